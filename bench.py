@@ -20,10 +20,17 @@ hipGraph with the RCCL collectives captured inside it, under a watchdog: if the 
 measurement is what gets printed.
 
 Prints ONE JSON line on rank 0.  `value` = env steps of all ranks / wall time of the K timed steps (inputs resident in HBM; the
-tree is generated and uploaded before the timed region).  `roofline` is for the kernel that takes the largest share of the step,
+tree is generated and uploaded before the timed region); `ms_per_step` = wall time of the K timed steps / K.  A plain run sets up,
+primes and warms up, times the K steps and prints the line; everything else it can measure runs only with --full:
+`roofline` is for the kernel that takes the largest share of the step,
 its launches bracketed with hipEvents on the launching stream in an eager (un-captured) leg of the same steps right after the
 timed region (events cannot sit inside a replayed graph); `kernels` lists every bracketed kernel of the step the same way.
 `cpu_baseline` times the CPU port (oracle/port.py: C oracle + PyTorch-CPU MLP) of the same step on a bounded sample, rank 0, N = 1.
+`other_modes`, the rollout alone, K1, the host enqueue cost, the side legs of the default line and, at N > 1, the all-reduce and the
+one-GPU base leg are --full as well.
+
+--dump-outputs DIR writes, right after the timed steps, what the last timed step handed its caller (dump_outputs below) as
+DIR/<name>.npy; the same arguments give the same inputs in every run (seeded tree, nets and rollout noise).
 """
 import argparse
 import json
@@ -143,6 +150,12 @@ def main():
     ap.add_argument("--no-side-legs", action="store_true",
                     help="skip the legs the default one-GPU line carries beside `value`: configs[3], dedup off, a sharp policy, 2^19 / 2^22 lanes")
     ap.add_argument("--side-steps", type=int, default=200, help="timed replays of each side leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can carry: host enqueue cost, per-kernel timings and the "
+                         "roofline, other_modes, the rollout alone, K1, the side legs, the CPU baseline; N > 1: the all-reduce and the "
+                         "one-GPU base leg.  Default: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -265,19 +278,24 @@ def main():
     legs = {}
     if world == 1:
         elapsed = timed_leg(not args.no_graph)
+        if args.dump_outputs:
+            dump_outputs(rn, args.dump_outputs)
     else:
         # the eagerly enqueued step first: RCCL's ordinary path.  The captured step (collectives inside the graph) is measured after
         # everything the JSON line needs exists, under a watchdog (see below).
         elapsed = legs["eager"] = timed_leg(False)
+        if args.dump_outputs and args.no_graph and rank == 0:
+            dump_outputs(rn, args.dump_outputs)
     # host cost of enqueueing one step, measured with the queue kept short (a long un-synchronised run measures back-pressure)
     host_s, host_n = 0.0, min(64, args.steps)
-    for i in range(host_n):
-        h0 = time.perf_counter()
-        one_step()
-        host_s += time.perf_counter() - h0
-        if i % 4 == 3:
-            torch.cuda.synchronize()
-    fence()
+    if args.full:
+        for i in range(host_n):
+            h0 = time.perf_counter()
+            one_step()
+            host_s += time.perf_counter() - h0
+            if i % 4 == 3:
+                torch.cuda.synchronize()
+        fence()
     graph_state = getattr(rn, "_graph", None)
     replayed = bool(graph_state and graph_state.get("graph") is not None)
     T = rn.last_episodes.t_eff + 1
@@ -297,132 +315,134 @@ def main():
     default_mode = rn.tabular
     mode_now = rn._tabular_mode(T, local_batch)
 
-    # ---- per-kernel durations: the same steps again, eagerly, every kernel bracketed with hipEvents on the launching stream
     E = max(1, min(args.other_steps, args.steps))
-    rn.use_graph = False
-    for _ in range(2):
-        one_step()
-    fence()
-    rnad_hip.prof_enable(True)
-    EP = max(E, min(200, args.steps))  # steps of the bracketed leg (eager steps are host-paced: short legs see the clocks ramp)
-    for _ in range(EP):
-        one_step()
-    fence()
-    # (the default step's table launch also writes the row records: csrc/mlp_rows.hip; the lazy-rows step runs it for the value heads)
-    fused_rows = mode_now_is_true(rn, T, local_batch) and rnad_hip.mlp_rows_records_supported(A, args.width, rn._fold(), lazy_now)
-    fwd_name = "k_rows_forward_records (table forwards + row records)" + (" + k_mlp_forward (staged actor)" if lazy_now else "") if fused_rows else "k_mlp_forward"
-    names = {rnad_hip.PROF_OBSERVE: "k_observe", rnad_hip.PROF_ACT: "rollout (all kernels of Episodes.generate)",
-             rnad_hip.PROF_LEARN: "learner (all kernels between the forwards and the backward)", rnad_hip.PROF_MLP: fwd_name,
-             rnad_hip.PROF_MLP_BWD: "k_mlp_backward", rnad_hip.PROF_BUCKET_KEYS: "k_bucket_keys (with the sort tile's histogram)",
-             rnad_hip.PROF_BUCKET_SORT: "k_bucket_scan+scatter (+hist on the global-table fallback)", rnad_hip.PROF_BUCKET_ROLLOUT: "k_bucket_rollout",
-             rnad_hip.PROF_BUCKET_LEARN: "k_bucket_learn", rnad_hip.PROF_BUCKET_FINISH: "k_bucket_finish"}
-    prof = {}
-    for k, nm in names.items():
-        n, ms = rnad_hip.prof_read(k)
-        if n:
-            prof[k] = dict(name=nm, launches_per_step=n / EP, avg_launch_us=ms * 1e3 / n, us_per_step=ms * 1e3 / EP)
-    rnad_hip.prof_enable(False)
-    rn.use_graph = not args.no_graph
-    # rollout and learner in one launch (RNaD.fuse_rollout_learner, k_bucket_play_learn): booked under the learner's id, nothing under the rollout's
-    args.fused_play_learn = (mode_now is True and rnad_hip.PROF_BUCKET_LEARN in prof and rnad_hip.PROF_BUCKET_ROLLOUT not in prof)
-    # (the learner on the tree's leaf paths, DESIGN.md section 5.6: rollout and learner are two launches inside the same scope)
-    with rnad_hip.workspace_owner(rn._workspace_token()):  # (the trainer's own plan: no second LeafPaths on the default one)
-        args.leaf_paths = bool(args.fused_play_learn and rn._fuse_now() and rn._leaf_now(handle, local_batch, T) is not None)
-    if args.leaf_paths:
-        args.fused_play_learn = False
-        prof[rnad_hip.PROF_BUCKET_LEARN]["name"] = "k_bucket_play_count + k_bucket_learn_c<WEIGHTED> (rollout, then the learner on the tree's leaf paths)"
-    elif args.fused_play_learn:
-        prof[rnad_hip.PROF_BUCKET_LEARN]["name"] = "k_bucket_play_learn (rollout + learner of a work item in one launch)"
+    prof, variants, rollout_s, k1, allreduce_us = {}, {}, None, None, None
+    if args.full:
+        # ---- per-kernel durations: the same steps again, eagerly, every kernel bracketed with hipEvents on the launching stream
+        rn.use_graph = False
+        for _ in range(2):
+            one_step()
+        fence()
+        rnad_hip.prof_enable(True)
+        EP = max(E, min(200, args.steps))  # steps of the bracketed leg (eager steps are host-paced: short legs see the clocks ramp)
+        for _ in range(EP):
+            one_step()
+        fence()
+        # (the default step's table launch also writes the row records: csrc/mlp_rows.hip; the lazy-rows step runs it for the value heads)
+        fused_rows = mode_now_is_true(rn, T, local_batch) and rnad_hip.mlp_rows_records_supported(A, args.width, rn._fold(), lazy_now)
+        fwd_name = "k_rows_forward_records (table forwards + row records)" + (" + k_mlp_forward (staged actor)" if lazy_now else "") if fused_rows else "k_mlp_forward"
+        names = {rnad_hip.PROF_OBSERVE: "k_observe", rnad_hip.PROF_ACT: "rollout (all kernels of Episodes.generate)",
+                 rnad_hip.PROF_LEARN: "learner (all kernels between the forwards and the backward)", rnad_hip.PROF_MLP: fwd_name,
+                 rnad_hip.PROF_MLP_BWD: "k_mlp_backward", rnad_hip.PROF_BUCKET_KEYS: "k_bucket_keys (with the sort tile's histogram)",
+                 rnad_hip.PROF_BUCKET_SORT: "k_bucket_scan+scatter (+hist on the global-table fallback)", rnad_hip.PROF_BUCKET_ROLLOUT: "k_bucket_rollout",
+                 rnad_hip.PROF_BUCKET_LEARN: "k_bucket_learn", rnad_hip.PROF_BUCKET_FINISH: "k_bucket_finish"}
+        prof = {}
+        for k, nm in names.items():
+            n, ms = rnad_hip.prof_read(k)
+            if n:
+                prof[k] = dict(name=nm, launches_per_step=n / EP, avg_launch_us=ms * 1e3 / n, us_per_step=ms * 1e3 / EP)
+        rnad_hip.prof_enable(False)
+        rn.use_graph = not args.no_graph
+        # rollout and learner in one launch (RNaD.fuse_rollout_learner, k_bucket_play_learn): booked under the learner's id, nothing under the rollout's
+        args.fused_play_learn = (mode_now is True and rnad_hip.PROF_BUCKET_LEARN in prof and rnad_hip.PROF_BUCKET_ROLLOUT not in prof)
+        # (the learner on the tree's leaf paths, DESIGN.md section 5.6: rollout and learner are two launches inside the same scope)
+        with rnad_hip.workspace_owner(rn._workspace_token()):  # (the trainer's own plan: no second LeafPaths on the default one)
+            args.leaf_paths = bool(args.fused_play_learn and rn._fuse_now() and rn._leaf_now(handle, local_batch, T) is not None)
+        if args.leaf_paths:
+            args.fused_play_learn = False
+            prof[rnad_hip.PROF_BUCKET_LEARN]["name"] = "k_bucket_play_count + k_bucket_learn_c<WEIGHTED> (rollout, then the learner on the tree's leaf paths)"
+        elif args.fused_play_learn:
+            prof[rnad_hip.PROF_BUCKET_LEARN]["name"] = "k_bucket_play_learn (rollout + learner of a work item in one launch)"
 
-    # ---- the same step in the other net-evaluation modes of RNaD (reported separately, NOT `value`), eager
-    variants = {}
-    for name, mode in (("dense_nets", False), ("forward", "forward"), ("tabular_nets", True)):
-        if world > 1:
-            break  # the N > 1 lines are for the scaling curve: the other modes are reported at N = 1
-        if mode == default_mode or (mode and not rn._fused_mlp()):
-            continue
-        rn.tabular = mode
-        if rn._tabular_mode(T, local_batch) != mode:
-            continue
-        one_step()
-        one_step()
-        variants[name] = timed(E)[0]
-    rn.tabular = default_mode
-    # rollout alone (Episodes.generate as RNaD.train_step calls it), outside the headline timed region
-    actor_tables = rn._table_outputs(0.5, fold=args.fold) if mode_now is True else None
-    fence()
-    t_r = time.perf_counter()
-    for i in range(E):
-        ep = Episodes(tree, local_batch, seed=1000 + i, lane_offset=rank * local_batch, obs_half=args.obs_half)
-        ep.generate(rn.net, trim=False, skip_absorbed=True, store_values=False, tabular=bool(mode_now), bucketed=mode_now is True,
-                    logits_table=actor_tables["logit"] if actor_tables else None)
-    fence()
-    rollout_s = time.perf_counter() - t_r
-    # K1, the API's episode-gather kernel (States.observations): not part of the default step any more (observations are
-    # materialised on demand); timed on its own over the T steps of the last rollout
-    k1 = None
-    if rank == 0:
-        # every launch writes its own [B, 2, A, A] slice of a [T, B, 2, A, A] buffer (906 MB at T = 12, fp32: beyond the 256 MiB Infinity Cache)
-        obs = torch.empty((T, local_batch, 2, A, A), dtype=torch.float16 if args.obs_half else torch.float32, device=device)
-        bits = torch.empty((T, local_batch), dtype=torch.uint8, device=device)
-        idx_all = ep.indices
-        for t in range(T):
-            rnad_hip.observe(handle, idx_all[t], t & 1, obs=obs[t], half=args.obs_half, mask_bits=bits[t])
-        fence_local = torch.cuda.synchronize
-        fence_local()
-        rnad_hip.prof_enable([rnad_hip.PROF_OBSERVE])
-        for _ in range(3):
+        # ---- the same step in the other net-evaluation modes of RNaD (reported separately, NOT `value`), eager
+        variants = {}
+        for name, mode in (("dense_nets", False), ("forward", "forward"), ("tabular_nets", True)):
+            if world > 1:
+                break  # the N > 1 lines are for the scaling curve: the other modes are reported at N = 1
+            if mode == default_mode or (mode and not rn._fused_mlp()):
+                continue
+            rn.tabular = mode
+            if rn._tabular_mode(T, local_batch) != mode:
+                continue
+            one_step()
+            one_step()
+            variants[name] = timed(E)[0]
+        rn.tabular = default_mode
+        # rollout alone (Episodes.generate as RNaD.train_step calls it), outside the headline timed region
+        actor_tables = rn._table_outputs(0.5, fold=args.fold) if mode_now is True else None
+        fence()
+        t_r = time.perf_counter()
+        for i in range(E):
+            ep = Episodes(tree, local_batch, seed=1000 + i, lane_offset=rank * local_batch, obs_half=args.obs_half)
+            ep.generate(rn.net, trim=False, skip_absorbed=True, store_values=False, tabular=bool(mode_now), bucketed=mode_now is True,
+                        logits_table=actor_tables["logit"] if actor_tables else None)
+        fence()
+        rollout_s = time.perf_counter() - t_r
+        # K1, the API's episode-gather kernel (States.observations): not part of the default step any more (observations are
+        # materialised on demand); timed on its own over the T steps of the last rollout
+        k1 = None
+        if rank == 0:
+            # every launch writes its own [B, 2, A, A] slice of a [T, B, 2, A, A] buffer (906 MB at T = 12, fp32: beyond the 256 MiB Infinity Cache)
+            obs = torch.empty((T, local_batch, 2, A, A), dtype=torch.float16 if args.obs_half else torch.float32, device=device)
+            bits = torch.empty((T, local_batch), dtype=torch.uint8, device=device)
+            idx_all = ep.indices
             for t in range(T):
                 rnad_hip.observe(handle, idx_all[t], t & 1, obs=obs[t], half=args.obs_half, mask_bits=bits[t])
-        n_obs, obs_ms = rnad_hip.prof_read(rnad_hip.PROF_OBSERVE)
-        rnad_hip.prof_enable(False)
-        # what plain streams reach on this GPU over the same buffer (the practical ceiling K1's fraction of the 8 TB/s spec peak is to be
-        # read against): torch.fill_ (stores only) and torch.copy_ (a read and a write stream)
-        practical = {}
-        try:
-            flat = obs.view(-1)
-            half_n = flat.numel() // 2
-            for name, fn, moved in (("fill", lambda: flat.fill_(0.0), flat.numel() * flat.element_size()),
-                                    ("copy", lambda: flat[:half_n].copy_(flat[half_n: 2 * half_n]), 2 * half_n * flat.element_size())):
-                for _ in range(2):
-                    fn()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(10):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                practical[name + "_TBps"] = moved / (e0.elapsed_time(e1) * 1e-3 / 10) / 1e12
-        except Exception as err:
-            practical = {"error": str(err)[:200]}
-        k1 = (n_obs, obs_ms, practical)
-        del obs, bits
-    if world > 1:
-        t = torch.tensor([rollout_s, host_s], device=device, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        rollout_s, host_s = t.tolist()
-    # ---- N > 1: what the step's one exposed collective costs on THIS node -- the 43 KB gradient bucket all-reduced back to back on the
-    # step's stream, eagerly and replayed from a graph of its own (side_legs' `strong_scaling.predicted` ASSUMES ALLREDUCE_US_ASSUMED for it)
-    allreduce_us = None
-    if world > 1:
-        try:
-            n_params = sum(p_.numel() for p_ in rn.net.parameters())
-            bucket = torch.zeros((n_params,), dtype=torch.float32, device=device)
-            for _ in range(20):
-                dist.all_reduce(bucket)
-            fence()
-            t_a = time.perf_counter()
-            for _ in range(200):
-                dist.all_reduce(bucket)
-            torch.cuda.synchronize()
-            allreduce_us = {"bytes": 4 * n_params, "eager_back_to_back_us": (time.perf_counter() - t_a) / 200 * 1e6, "calls": 200,
-                            "what": "dist.all_reduce of the flat gradient bucket, 200 calls between two fences, max over ranks below"}
-            t = torch.tensor([allreduce_us["eager_back_to_back_us"]], device=device, dtype=torch.float64)
+            fence_local = torch.cuda.synchronize
+            fence_local()
+            rnad_hip.prof_enable([rnad_hip.PROF_OBSERVE])
+            for _ in range(3):
+                for t in range(T):
+                    rnad_hip.observe(handle, idx_all[t], t & 1, obs=obs[t], half=args.obs_half, mask_bits=bits[t])
+            n_obs, obs_ms = rnad_hip.prof_read(rnad_hip.PROF_OBSERVE)
+            rnad_hip.prof_enable(False)
+            # what plain streams reach on this GPU over the same buffer (the practical ceiling K1's fraction of the 8 TB/s spec peak is to be
+            # read against): torch.fill_ (stores only) and torch.copy_ (a read and a write stream)
+            practical = {}
+            try:
+                flat = obs.view(-1)
+                half_n = flat.numel() // 2
+                for name, fn, moved in (("fill", lambda: flat.fill_(0.0), flat.numel() * flat.element_size()),
+                                        ("copy", lambda: flat[:half_n].copy_(flat[half_n: 2 * half_n]), 2 * half_n * flat.element_size())):
+                    for _ in range(2):
+                        fn()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(10):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    practical[name + "_TBps"] = moved / (e0.elapsed_time(e1) * 1e-3 / 10) / 1e12
+            except Exception as err:
+                practical = {"error": str(err)[:200]}
+            k1 = (n_obs, obs_ms, practical)
+            del obs, bits
+        if world > 1:
+            t = torch.tensor([rollout_s, host_s], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            allreduce_us["eager_back_to_back_us"] = float(t.item())
-            del bucket
-        except Exception as err:  # (never the reason a scaling line is lost)
-            allreduce_us = {"error": str(err)[:300]}
+            rollout_s, host_s = t.tolist()
+        # ---- N > 1: what the step's one exposed collective costs on THIS node -- the 43 KB gradient bucket all-reduced back to back on the
+        # step's stream, eagerly and replayed from a graph of its own (side_legs' `strong_scaling.predicted` ASSUMES ALLREDUCE_US_ASSUMED for it)
+        allreduce_us = None
+        if world > 1:
+            try:
+                n_params = sum(p_.numel() for p_ in rn.net.parameters())
+                bucket = torch.zeros((n_params,), dtype=torch.float32, device=device)
+                for _ in range(20):
+                    dist.all_reduce(bucket)
+                fence()
+                t_a = time.perf_counter()
+                for _ in range(200):
+                    dist.all_reduce(bucket)
+                torch.cuda.synchronize()
+                allreduce_us = {"bytes": 4 * n_params, "eager_back_to_back_us": (time.perf_counter() - t_a) / 200 * 1e6, "calls": 200,
+                                "what": "dist.all_reduce of the flat gradient bucket, 200 calls between two fences, max over ranks below"}
+                t = torch.tensor([allreduce_us["eager_back_to_back_us"]], device=device, dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                allreduce_us["eager_back_to_back_us"] = float(t.item())
+                del bucket
+            except Exception as err:  # (never the reason a scaling line is lost)
+                allreduce_us = {"error": str(err)[:300]}
 
     # read back NOW: emit() may be called from the watchdog thread while the device queue is stuck
     alive = rn.last_episodes.alive.cpu().numpy()[:T]
@@ -430,7 +450,7 @@ def main():
     # ---- strong scaling: the N = 1 point of this curve -- the SAME global batch on rank 0's GPU alone (no collectives), same mode,
     # same replayed graph; the other ranks wait at the barrier below
     base = None
-    if world > 1 and args.scaling == "strong" and not args.no_base_leg:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_base_leg:
         if rank == 0:
             try:
                 solo, _, solo_step = make_trainer(global_batch, "bench-solo", data_parallel=False)
@@ -455,7 +475,7 @@ def main():
     # ---- side legs (one GPU, the default workload only; outside the timed region, each its own trainer, replayed graphs)
     side = {}
     default_line = (world == 1 and (A, C, depth, tuple(args.prune), args.width, args.batch_log2) == (3, 1, 6, (0, 0), 256, 20)
-                    and args.net_mode == "default" and not args.no_graph and not args.obs_half and not args.no_side_legs)
+                    and args.net_mode == "default" and not args.no_graph and not args.obs_half and not args.no_side_legs and args.full)
     if default_line:
         side = side_legs(make_trainer, tree, args, device)
 
@@ -482,8 +502,6 @@ def main():
                 "forward": "forward evaluations once per (player, state) row and gathered per slot; backward per slot; bit-identical to dense",
                 True: "nets evaluated once per (player, state) row; bucket-ordered rollout; per-slot gradients summed per row in LDS (64-bit "
                       "fixed point, reproducible); one backward over the rows; gradients equal the dense ones up to fp32 summation order"}
-        kernels = kernel_report(prof, A, C, args, local_batch, T, live_slots, tree, mode_now)
-        dominant = max((k for k in kernels.values() if k.get("single_kernel")), key=lambda k: k["us_per_step"], default=None)
         out = {
             "metric": "env_steps_per_sec (rollout + R-NaD update, one iteration of learn/rnad.py:495-526 per step)",
             "value": env_steps / elapsed,
@@ -510,12 +528,9 @@ def main():
                                   if tree.handle().uniform_length else " + 2 normalisers)"),
             },
             "updates_per_sec": args.steps / elapsed,
-            "host_enqueue_ms_per_step": host_s / host_n * 1e3,
             "net_evaluation": {"mode": f"RNaD.tabular = {default_mode!r}" + (" (default)" if args.net_mode == "default" else ""),
                                "in_effect": repr(mode_now), "what": what[mode_now],
                                "step_replayed_from_hipGraph": replayed, "compact_trajectory": bool(args.compact_in_effect),
-                               "rollout_and_learner_in_one_launch": bool(getattr(args, "fused_play_learn", False)),
-                               "learner_on_leaf_paths": bool(getattr(args, "leaf_paths", False)),
                                # (RNaD.distinct_trajectories: by itself only after RNaD.DISTINCT_AFTER = 4096 updates -- not within a default run)
                                "learner_on_distinct_trajectories_at_the_end": bool(rn._fuse_now() and rn._distinct_now()),
                                "lazy_rows_visited": args.visited_rows or None, "staged_policy_rows": args.policy_rows or None,
@@ -523,17 +538,26 @@ def main():
                                "legal_fold": args.fold,
                                "table_rows": 2 * handle.S,  # (player, state) rows of the tree: what the nets are evaluated on without dedup
                                "slots": T * local_batch},
-            "other_modes": {name: {"env_steps_per_sec": global_batch * T_ref * E / sec, "updates_per_sec": E / sec,
-                                   "ms_per_step": sec / E * 1e3, "steps": E,
-                                   "what": what[{"dense_nets": False, "forward": "forward", "tabular_nets": True}[name]]}
-                            for name, sec in variants.items()},
-            "rollout_env_steps_per_sec": global_batch * T_ref * E / rollout_s,
-            "rollout_ms_per_step": rollout_s / E * 1e3,
-            "roofline": roofline_of(dominant),
-            "kernels": kernels,
-            "k1_observe": k1_report(k1, A, args, local_batch),
             "setup": {"tree_generate_and_upload_s": setup_tree_s, "tree_table_bytes": handle.table_bytes},
         }
+        if args.full:
+            # (which launches ran is read off the bracketed leg: known with --full only)
+            out["net_evaluation"].update(rollout_and_learner_in_one_launch=bool(getattr(args, "fused_play_learn", False)),
+                                         learner_on_leaf_paths=bool(getattr(args, "leaf_paths", False)))
+            kernels = kernel_report(prof, A, C, args, local_batch, T, live_slots, tree, mode_now)
+            dominant = max((k for k in kernels.values() if k.get("single_kernel")), key=lambda k: k["us_per_step"], default=None)
+            out.update({
+                "host_enqueue_ms_per_step": host_s / host_n * 1e3,
+                "other_modes": {name: {"env_steps_per_sec": global_batch * T_ref * E / sec, "updates_per_sec": E / sec,
+                                       "ms_per_step": sec / E * 1e3, "steps": E,
+                                       "what": what[{"dense_nets": False, "forward": "forward", "tabular_nets": True}[name]]}
+                                for name, sec in variants.items()},
+                "rollout_env_steps_per_sec": global_batch * T_ref * E / rollout_s,
+                "rollout_ms_per_step": rollout_s / E * 1e3,
+                "roofline": roofline_of(dominant),
+                "kernels": kernels,
+                "k1_observe": k1_report(k1, A, args, local_batch),
+            })
         if world > 1:
             out["legs_ms_per_step"] = {k: v / args.steps * 1e3 for k, v in legs.items()}
             if not rehearsal:
@@ -556,7 +580,7 @@ def main():
             if note:
                 out["note"] = note
         out.update(side)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(tree, args, T)
         print(json.dumps(out), flush=True)
 
@@ -584,6 +608,8 @@ def main():
         flag = torch.tensor([1 if (g and g.get("graph") is not None) else 0], dtype=torch.int32, device=device)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         watchdog.cancel()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(rn, args.dump_outputs)
         if int(flag.item()) == 1 and graph_sec < elapsed:
             emit(graph_sec, True)
         else:
@@ -595,6 +621,47 @@ def main():
 
 FP32_PEAK_TFLOPS = 157.3  # fp32 MFMA == fp32 vector peak (/opt/skills/guides/MI355X_MICROARCH.md)
 ALLREDUCE_US_ASSUMED = 15.0  # one 43 KB all-reduce over xGMI, exposed between backward and optimiser (latency-bound)
+
+
+DUMP_LANES = 1 << 16         # lanes of the played batch --dump-outputs writes (a fixed, seeded sample: 2^20 lanes are ~400 MB)
+DUMP_MAX_BYTES = 64 << 20    # everything --dump-outputs writes together
+
+
+def dump_outputs(rn, out_dir):
+    """--dump-outputs: what the last step handed its caller, one DIR/<name>.npy per array, float32 (float64 for state ids and lane ids):
+      net.<param>, net_target.<param>   the learner net and its EMA target after the step's update (every entry of the state_dict)
+      lanes                             the sampled lanes (0-based within the batch): DUMP_LANES of them, drawn with a fixed seed
+      indices, action_idx, rewards      [T, n] state ids, action ids and rewards of the batch the step played, at the sampled lanes
+      policy                            [T, n, A] the acting policy at the sampled lanes
+    The batch is put back in lane order first (a bucket-ordered rollout keeps lane lane_ids[j] in column j)."""
+    import numpy as np
+
+    torch.cuda.synchronize()
+    arrays = {}
+    for prefix, module in (("net", rn.net), ("net_target", rn.net_target)):
+        for name, t in module.state_dict().items():
+            arrays[f"{prefix}.{name}"] = t.detach().to(torch.float32).cpu().numpy()
+    ep = rn.last_episodes
+    T, B, A = ep.t_eff + 1, ep.batch_size, rn.tree.max_actions
+    left = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values())
+    per_lane = 8 + T * (8 + 4 + 4 + 4 * A)  # lanes f64; per step: indices f64, action_idx f32, rewards f32, policy f32 x A
+    n = min(B, DUMP_LANES, left // per_lane)
+    lanes = np.sort(np.random.default_rng(0).choice(B, n, replace=False)) if n < B else np.arange(B)
+    dev = ep.indices.device
+    column = torch.arange(B, device=dev)
+    if ep.lane_ids is not None:
+        column = torch.empty_like(column)
+        column[ep.lane_ids.long()] = torch.arange(B, device=dev)
+    cols = column[torch.as_tensor(lanes, device=dev)]
+    arrays["lanes"] = lanes.astype(np.float64)
+    arrays["indices"] = ep.indices[:T][:, cols].cpu().numpy().astype(np.float64)
+    arrays["action_idx"] = ep.action_idx[:T][:, cols].cpu().numpy().astype(np.float32)
+    arrays["rewards"] = ep.rewards[:T][:, cols].to(torch.float32).cpu().numpy()
+    arrays["policy"] = ep.policy[:T][:, cols].to(torch.float32).cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def side_legs(make_trainer, tree, args, device):

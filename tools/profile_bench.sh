@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 tag=$1; shift
 out=$R/gpurun_out/prof_$tag
 mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python $R/bench.py --no-cpu-baseline "$@" > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python $R/bench.py --full --no-cpu-baseline "$@" > $out/bench.log 2>&1
 grep "^{" $out/bench.log | tail -1 > $R/gpurun_out/${tag}_bench_profiled.json.log
 f=$(find $out -name '*kernel_stats.csv' | head -1)
 cp "$f" $R/gpurun_out/${tag}_bench_kernel_stats.csv

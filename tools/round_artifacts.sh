@@ -33,11 +33,11 @@ cp $O/${tag}_pmc_c4.json $O/${tag}_pmc_b22.json profiles/
 python tools/isa_mix.py --issue $O/${tag}_valu_issue.json > $O/${tag}_isa_mix.log 2>&1
 cp profiles/${tag}_isa_mix.json profiles/${tag}_valu_issue.json $O/
 # 1. headline bench (default flags) + the per-GPU share of an 8-GPU run + configs[3] + fp16 observations
-python bench.py > $O/${tag}_bench.log 2>&1; grep '^{' $O/${tag}_bench.log | tail -1 > $O/${tag}_bench.json.log
-python bench.py --batch-log2 19 --steps 1000 --no-cpu-baseline > $O/${tag}_bench_b19.log 2>&1; grep '^{' $O/${tag}_bench_b19.log | tail -1 > $O/${tag}_bench_b19.json.log
-python bench.py --batch-log2 22 --steps 500 --no-cpu-baseline > $O/${tag}_bench_b22.log 2>&1; grep '^{' $O/${tag}_bench_b22.log | tail -1 > $O/${tag}_bench_b22.json.log
-python bench.py --actions 5 --transitions 4 --depth 8 --prune 7 8 --threshold 0.1 --steps 200 --no-cpu-baseline > $O/${tag}_bench_c4.log 2>&1; grep '^{' $O/${tag}_bench_c4.log | tail -1 > $O/${tag}_bench_c4.json.log
-python bench.py --obs-half --steps 500 --no-cpu-baseline > $O/${tag}_bench_half.log 2>&1; grep '^{' $O/${tag}_bench_half.log | tail -1 > $O/${tag}_bench_half.json.log
+python bench.py --full > $O/${tag}_bench.log 2>&1; grep '^{' $O/${tag}_bench.log | tail -1 > $O/${tag}_bench.json.log
+python bench.py --batch-log2 19 --steps 1000 --no-cpu-baseline --full > $O/${tag}_bench_b19.log 2>&1; grep '^{' $O/${tag}_bench_b19.log | tail -1 > $O/${tag}_bench_b19.json.log
+python bench.py --batch-log2 22 --steps 500 --no-cpu-baseline --full > $O/${tag}_bench_b22.log 2>&1; grep '^{' $O/${tag}_bench_b22.log | tail -1 > $O/${tag}_bench_b22.json.log
+python bench.py --actions 5 --transitions 4 --depth 8 --prune 7 8 --threshold 0.1 --steps 200 --no-cpu-baseline --full > $O/${tag}_bench_c4.log 2>&1; grep '^{' $O/${tag}_bench_c4.log | tail -1 > $O/${tag}_bench_c4.json.log
+python bench.py --obs-half --steps 500 --no-cpu-baseline --full > $O/${tag}_bench_half.log 2>&1; grep '^{' $O/${tag}_bench_half.log | tail -1 > $O/${tag}_bench_half.json.log
 # 2. rocprofv3 kernel trace of the same bench command, and of the replayed step alone
 bash tools/profile_bench.sh ${tag} --steps 300 > $O/${tag}_profile.log 2>&1
 tools/step_kernels.sh > $O/${tag}_step_kernels.txt 2>&1
