@@ -31,6 +31,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <utility>
 
 using namespace rnad;
 using namespace rnad::dev;
@@ -82,6 +83,37 @@ constexpr int kMinSortTile = kSortThreads * kPlayLds > 1024 ? kSortThreads * kPl
     }
 
 inline unsigned blocks_for(int64_t n, int per = kThreads) { return (unsigned)((n + per - 1) / per); }
+
+// The switches this file takes from the environment (tuning knobs, tests).  read_switches() is called afresh at the top of every C-ABI
+// call that uses one and the call hands its copy down: tests/test_hip_bucket.py and tools/*_sweep.sh set them between calls of one
+// process, and rnad_hip.plan_knobs() keys the Python caches on three of them.  Nothing below reads the environment, nothing caches a value
+// (the two caches on the tree that a switch reaches are keyed on it: plan_rows, plan_sized -- and RNAD_KEYS_STAGE_BYTES, see get_cut).
+struct Switch {
+    bool set;  // the variable exists
+    int v;     // atoi of its text
+};
+struct Switches {
+    Switch bucket_rows;       // RNAD_BUCKET_ROWS: forces the table size of the cut (make_plan)
+    Switch bucket_chunk;      // RNAD_BUCKET_CHUNK: lanes per work item of the learner (make_plan)
+    Switch sort_tile;         // RNAD_SORT_TILE: lanes per workgroup of the sort passes (make_plan)
+    Switch keys_stage_bytes;  // RNAD_KEYS_STAGE_BYTES: LDS budget of the hybrid keys walk's tables (get_cut)
+    Switch keys_global;       // RNAD_KEYS_GLOBAL != 0: the keys walk on the global tables (tests: the fallback on any tree)
+    Switch keys_lds;          // RNAD_KEYS_LDS = 0: not the walk with all tables in LDS (tests: the hybrid walk on small trees)
+    Switch keys_hybrid;       // RNAD_KEYS_HYBRID = 0: not the hybrid walk
+    Switch expand_blocks;     // RNAD_EXPAND_BLOCKS: workgroups of the copies that ride in the scan launch
+    Switch scatter_rows;      // RNAD_SCATTER_ROWS: counter rows of the scatter
+    Switch fused_distinct;    // RNAD_FUSED_DISTINCT = 0 / 1: overrides the caller's RNAD_PLAY_LEARN_DISTINCT
+    Switch fused_chunk;       // RNAD_FUSED_CHUNK: lanes per work item of k_bucket_play_learn on distinct trajectories
+};
+Switches read_switches() {
+    auto read = [](const char *name) {
+        const char *text = getenv(name);
+        return text ? Switch{true, atoi(text)} : Switch{false, 0};
+    };
+    return {read("RNAD_BUCKET_ROWS"), read("RNAD_BUCKET_CHUNK"), read("RNAD_SORT_TILE"), read("RNAD_KEYS_STAGE_BYTES"),  // (the members' order)
+            read("RNAD_KEYS_GLOBAL"), read("RNAD_KEYS_LDS"), read("RNAD_KEYS_HYBRID"), read("RNAD_EXPAND_BLOCKS"),
+            read("RNAD_SCATTER_ROWS"), read("RNAD_FUSED_DISTINCT"), read("RNAD_FUSED_CHUNK")};
+}
 
 struct Plan {
     const BucketCut *cut = nullptr;
@@ -222,8 +254,9 @@ bool cut_fits(const HostCut &c) { return c.n_buckets <= kMaxBuckets && c.n_upper
 
 // The cut on the device, cached with the handle.  nullptr: HIP allocation failed.  (Called from make_plan for the CHOSEN cut only; the
 // planner's candidates live on the host.  k_upper_walk runs on the null stream: rnad_bucket_plan is what a caller invokes before it
-// captures a step.)
-const BucketCut *get_cut(const rnad_tree_t *tree, int rows) {
+// captures a step.)  RNAD_KEYS_STAGE_BYTES takes effect while a cut is built: the cut, kept per table size, then holds what the call
+// that happened to build it saw.
+const BucketCut *get_cut(const rnad_tree_t *tree, int rows, const Switches &sw) {
     auto it = tree->cuts.find(rows);
     if (it != tree->cuts.end()) return &it->second;
     HostCut h = build_cut(tree, rows);
@@ -261,7 +294,7 @@ const BucketCut *get_cut(const rnad_tree_t *tree, int rows) {
         const int AAC = tree->A * tree->A * tree->C;
         const size_t per_state = (size_t)AAC * sizeof(UpperWalk) + 2 * (size_t)((tree->A + 3) & ~3) * sizeof(float);
         size_t budget = kKeysLds;
-        if (const char *e = getenv("RNAD_KEYS_STAGE_BYTES")) budget = (size_t)std::max(0, atoi(e));  // (tests: partial staging on small trees)
+        if (sw.keys_stage_bytes.set) budget = (size_t)std::max(0, sw.keys_stage_bytes.v);  // (tests: partial staging on small trees)
         const size_t fixed = (size_t)cut.n_upper * sizeof(int32_t) + 16;
         std::vector<std::vector<int32_t>> by_level;
         for (int i = 0; i < cut.n_upper; ++i) {
@@ -335,18 +368,17 @@ int choose_rows(const rnad_tree_t *tree, int64_t B, int forced, int rows_max) {
     return chosen;
 }
 
-bool make_plan(const rnad_tree_t *tree, int64_t B, Plan &p) {
+bool make_plan(const rnad_tree_t *tree, int64_t B, const Switches &sw, Plan &p) {
     if (!tree->contiguous_subtrees || B < 1 || B > ((int64_t)1 << kLaneBits)) return false;
     const int path_words = kMaxPath * kPathSlots * ((tree->A + 1) | 1);  // u64 words of the path region (slot stride odd: distinct banks)
     const int rows_max = (kLearnLds / 8 - path_words) / (2 * ((tree->A + 1) | 1));
-    const char *force = getenv("RNAD_BUCKET_ROWS");
-    const int forced = force ? std::max(atoi(force), -1) : 0;
-    if (force && forced < 1) return false;
+    const int forced = sw.bucket_rows.set ? std::max(sw.bucket_rows.v, -1) : 0;
+    if (sw.bucket_rows.set && forced < 1) return false;
     const auto key = std::make_pair(B, forced);
     auto it = tree->plan_rows.find(key);
     if (it == tree->plan_rows.end()) it = tree->plan_rows.emplace(key, choose_rows(tree, B, forced, rows_max)).first;
     if (it->second == 0) return false;
-    const BucketCut *chosen = get_cut(tree, it->second);
+    const BucketCut *chosen = get_cut(tree, it->second, sw);
     if (!chosen) return false;
     p.cut = chosen;
     // the path region holds the rows of THIS cut's upper steps (not kMaxPath of them: LDS per workgroup bounds the resident waves)
@@ -366,12 +398,12 @@ bool make_plan(const rnad_tree_t *tree, int64_t B, Plan &p) {
         // of all bucket totals: ~9 us of the scatter whatever the tile) is then paid half as often
         if ((B + p.tile - 1) / p.tile > 512) p.tile = 8192;
     }
-    if (const char *t = getenv("RNAD_SORT_TILE")) {  // tuning knob / tests
-        const int v = atoi(t);
+    if (sw.sort_tile.set) {  // tuning knob / tests
+        const int v = sw.sort_tile.v;
         if ((v == 1024 || v == 2048 || v == 4096 || v == 8192) && v >= kMinSortTile) p.tile = v;
     }
     p.sort_blocks = (int)((B + p.tile - 1) / p.tile);
-    if (const char *c = getenv("RNAD_BUCKET_CHUNK")) p.chunk = std::max(64, atoi(c));  // tuning knob
+    if (sw.bucket_chunk.set) p.chunk = std::max(64, sw.bucket_chunk.v);  // tuning knob
     p.max_items = (int64_t)chosen->n_buckets + B / p.chunk + 1 + 7;  // (+ 7: the XCD-aware item mapping needs 8 * ceil(n / 8) workgroups)
     p.forced = forced;
     return true;
@@ -385,9 +417,14 @@ void note_sized(const rnad_tree_t *tree, int64_t B, const Plan &p) { tree->plan_
 bool sized_for(const rnad_tree_t *tree, int64_t B, const Plan &p) {
     return tree->plan_sized.count(std::make_tuple(B, p.forced, p.tile, p.chunk)) != 0;
 }
-#define RNAD_REQUIRE_SIZED(tree_, B_, p_)                                                                                                  \
-    RNAD_REQUIRE(sized_for(tree_, B_, p_), "RNAD_SORT_TILE / RNAD_BUCKET_CHUNK / RNAD_BUCKET_ROWS differ from what rnad_bucket_plan sized " \
-                                            "this batch's scratch buffers for (tile %d, chunk %d): call rnad_bucket_plan again and reallocate", (p_).tile, (p_).chunk)
+
+// The plan of (tree, B) under this call's switches, or the error of entry point `who`; `sized`: one that reads or writes the scratch.
+int plan_for(const rnad_tree_t *tree, int64_t B, const Switches &sw, const char *who, bool sized, Plan &p) {
+    RNAD_REQUIRE(make_plan(tree, B, sw, p), "%s: this tree / batch cannot be bucketed (see rnad_bucket_plan)", who);
+    RNAD_REQUIRE(!sized || sized_for(tree, B, p), "RNAD_SORT_TILE / RNAD_BUCKET_CHUNK / RNAD_BUCKET_ROWS differ from what rnad_bucket_plan sized "
+                                                  "this batch's scratch buffers for (tile %d, chunk %d): call rnad_bucket_plan again and reallocate", p.tile, p.chunk);
+    return 0;
+}
 
 // Sum over the 64 lanes of a wave in integer arithmetic on the VALU's data-parallel primitives (no LDS traffic): an inclusive
 // scan within each row of 16 lanes (row_shr 1, 2, 4, 8), then row 15 -> next row (row_bcast15) and lane 31 -> rows 2, 3
@@ -521,16 +558,6 @@ struct StageOut {
 };
 constexpr int kStageRootBits = 26;  // S <= 2^26 states; kMaxPath = 32 steps fit the 6 bits above
 __host__ __device__ inline uint32_t stage_stamp(uint64_t seed) { return ((uint32_t)seed ^ (uint32_t)(seed >> 32)) | 1u; }
-StageOut carve_stage(void *stage, int64_t B, int64_t S) {
-    StageOut st;
-    if (!stage) return st;
-    st.counts = (unsigned long long *)stage;
-    st.root = (uint32_t *)(st.counts + 2);
-    st.sorted = st.root + B;
-    st.mark0 = st.sorted + B;
-    st.mark1 = st.mark0 + S;
-    return st;
-}
 
 #ifndef RNAD_PLAY
 #define RNAD_PLAY 2
@@ -2725,31 +2752,128 @@ FixedPoint fixed_point_for(const rnad_learn_params_t &hp) {
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------- workspaces
+// Each of the three caller-owned workspaces has one struct of typed pointers and one carve function, the only place its offsets are
+// computed; the byte count a caller is told to allocate (rnad_bucket_plan out[5], out[6]; rnad_bucket_stage_bytes) is the end of the
+// same carving from a null base.  The layouts are part of the contract with the callers and with the kernels: they do not move.
+namespace {
+struct Carver {
+    uintptr_t at;
+    template <class T>
+    T *take(int64_t n) {
+        T *first = (T *)at;
+        at += (uintptr_t)n * sizeof(T);
+        return first;
+    }
+};
+
+// The accumulators of the learner (zero before the first update; k_bucket_finish leaves them zero again).  learn/rnad.py all-reduces the
+// prefix acc | rep and clears the prefix acc by its own arithmetic, and k_bucket_finish finds its tickets behind the flag, at
+// overflow + 1 and overflow + 2.  `bytes` has always counted 16 bytes for the pair (overflow, ticket), which takes 8: the 8 spare bytes
+// are still handed out (they end up behind alive_rep).
+struct Accumulators {
+    unsigned long long *acc;  // [2S][A + 1] the rows' sums, 64-bit fixed point
+    unsigned long long *rep;  // [2][max(n_upper, 1)][kReplicas][A + 1] the upper rows' sums, spread over kReplicas copies
+    double *losses_raw;       // [4]
+    int32_t *overflow;        // the flag | the ticket | kTicketGroups group tickets (k_bucket_finish's last-workgroup election)
+    double *norm_rep;         // [kReplicas][2] the normalisers k_bucket_play_learn counts ...
+    int32_t *alive_rep;       // [kReplicas][kCompactSteps + 1] ... and its alive counts
+    int64_t bytes;
+};
+Accumulators carve_accumulators(void *base, const rnad_tree_t *tree, const Plan &p) {
+    const int64_t A1 = tree->A + 1;
+    Carver c{(uintptr_t)base};
+    Accumulators a;
+    a.acc = c.take<unsigned long long>(2 * tree->S * A1);
+    a.rep = c.take<unsigned long long>((int64_t)kReplicas * 2 * std::max(p.cut->n_upper, 1) * A1);
+    a.losses_raw = c.take<double>(4);
+    a.overflow = c.take<int32_t>(2 + kTicketGroups);  // (what follows is 8-byte aligned: kTicketGroups is even)
+    a.norm_rep = c.take<double>(2 * kReplicas);
+    a.alive_rep = c.take<int32_t>(kReplicas * (kCompactSteps + 1));
+    a.bytes = (int64_t)(c.at - (uintptr_t)base) + 8;
+    return a;
+}
+
+// The scratch of the rollout.  The compact rollout runs one workgroup per work item (k_bucket_rollout_items), the dense one a workgroup
+// per kThreads columns: either leaves one row of alive counts per workgroup, and alive_part holds the larger number of rows.
+int64_t alive_rows(int64_t B, const Plan &p, bool compact) { return compact ? p.max_items : (int64_t)blocks_for(B); }
+int64_t alive_rows_max(int64_t B, const Plan &p) { return std::max<int64_t>(p.max_items, (int64_t)blocks_for(B)); }
+struct Scratch {
+    unsigned long long *decisions;  // [B]
+    int32_t *keys;                  // [B]
+    int32_t *hist;                  // [sort_blocks][n_buckets]
+    int32_t *totals, *bucket_start; // [n_buckets] each
+    int32_t *alive_part;            // [alive_rows_max][T_cap + 1 <= kMaxSteps + 1]
+    float *policy;                  // [2S][(A + 3) & ~3] (16-byte aligned rows): the actor's policy per row when the caller hands logits
+    int64_t bytes;
+};
+Scratch carve_scratch(void *ws, const rnad_tree_t *tree, int64_t B, const Plan &p) {
+    const int64_t nb = p.cut->n_buckets;
+    Carver c{(uintptr_t)ws};
+    Scratch s;
+    s.decisions = c.take<unsigned long long>(B);
+    s.keys = c.take<int32_t>(B);
+    s.hist = c.take<int32_t>(p.sort_blocks * nb);
+    s.totals = c.take<int32_t>(nb);
+    s.bucket_start = c.take<int32_t>(nb);
+    s.alive_part = c.take<int32_t>(alive_rows_max(B, p) * (kMaxSteps + 1));
+    const uintptr_t pad = (0 - c.at) & 15;  // up to the next 16 bytes: it depends on the caller's base, so `bytes` leaves it out ...
+    c.at += pad;
+    s.policy = c.take<float>(2 * tree->S * ((tree->A + 3) & ~3));
+    s.bytes = (int64_t)(c.at - pad - (uintptr_t)ws) + 256;  // ... and adds 256 bytes of slack that cover it
+    return s;
+}
+
+// The stage buffer of a tabular actor's second staging level (StageOut travels to the kernels by value: its members are theirs, so the
+// byte count comes back beside it).  No buffer and no count asked: no staging.
+StageOut carve_stage(void *stage, int64_t B, int64_t S, int64_t *bytes = nullptr) {
+    StageOut st;
+    if (!stage && !bytes) return st;
+    Carver c{(uintptr_t)stage};
+    st.counts = c.take<unsigned long long>(2);
+    st.root = c.take<uint32_t>(B);
+    st.sorted = c.take<uint32_t>(B);
+    st.mark0 = c.take<uint32_t>(S);
+    st.mark1 = c.take<uint32_t>(S);
+    if (bytes) *bytes = (int64_t)(c.at - (uintptr_t)stage);
+    return st;
+}
+
+// REL = the type of a relative state under plan p
+#define RNAD_DISPATCH_REL(p_, ...)        \
+    if ((p_).rel_bytes == 1) {            \
+        using REL = uint8_t;              \
+        __VA_ARGS__;                      \
+    } else {                              \
+        using REL = uint16_t;             \
+        __VA_ARGS__;                      \
+    }
+
+// A launch with `lds` bytes of dynamic LDS: above 48 KB the kernel's limit has to be raised first.
+template <class... Params, class... Args>
+int launch_lds(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args &&...args) {
+    if (lds > 48 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, std::forward<Args>(args)...);
+    return 0;
+}
+}  // namespace
+
 // ---------------------------------------------------------------------------------------- entry points
 extern "C" int rnad_bucket_plan(const rnad_tree_t *tree, int64_t B, int64_t *out) {
     RNAD_REQUIRE(tree && out, "rnad_bucket_plan: null argument");
     Plan p;
-    if (!make_plan(tree, B, p)) {
+    if (!make_plan(tree, B, read_switches(), p)) {
         set_error("rnad_bucket_plan: this tree / batch cannot be bucketed (ids not DFS pre-order, no level whose subtree table fits "
                   "the LDS, or more than 2^%d lanes)", kLaneBits);
         return 3;
     }
-    const int64_t A1 = tree->A + 1;
-    const int nb = p.cut->n_buckets, nu = p.cut->n_upper;
     out[0] = p.cut->rows;
-    out[1] = nb;
-    out[2] = nu;
+    out[1] = p.cut->n_buckets;
+    out[2] = p.cut->n_upper;
     out[3] = p.cut->n_groups;
     out[4] = p.max_items;
-    // scratch of the rollout (bytes): decisions [B] u64 | keys [B] | hist [sort_blocks][n_buckets] | totals [n_buckets] | bucket_start [n_buckets] |
-    // alive_part [blocks][T_cap + 1 <= kMaxSteps + 1] | policy [2S][(A + 3) & ~3] (16-byte aligned rows)
-    out[5] = 8 * B + 4 * (B + (int64_t)p.sort_blocks * nb + 2 * (int64_t)nb + std::max<int64_t>(p.max_items, (int64_t)blocks_for(B)) * (kMaxSteps + 1) +
-                  2 * tree->S * ((tree->A + 3) & ~3)) + 256;
-    // accumulators of the learner (bytes, must be zero before the first update): acc [2S][A+1] u64 | rep [64][2][n_upper][A+1] u64 |
-    // losses_raw [4] f64 | overflow [1] i32
-    // | norm_rep [64][2] f64 | alive_rep [64][kCompactSteps + 1] i32 (the counts of rnad_rollout_learn_bucketed_compact)
-    out[6] = 8 * (2 * tree->S * A1 + (int64_t)kReplicas * 2 * std::max(nu, 1) * A1 + 4) + 16 + 4 * kTicketGroups +  // sums | loss sums | flag, ticket | group tickets
-             8 * 2 * kReplicas + 4 * kReplicas * (kCompactSteps + 1);
+    out[5] = carve_scratch(nullptr, tree, B, p).bytes;
+    out[6] = carve_accumulators(nullptr, tree, p).bytes;
     out[7] = p.lds;
     out[8] = p.rel_bytes;
     out[9] = p.tile;
@@ -2761,7 +2885,7 @@ extern "C" int rnad_bucket_plan(const rnad_tree_t *tree, int64_t B, int64_t *out
 extern "C" int rnad_bucket_map(const rnad_tree_t *tree, int64_t B, int32_t *bucket_of, int32_t *n_groups) {
     RNAD_REQUIRE(tree && bucket_of && n_groups, "rnad_bucket_map: null argument");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_bucket_map: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_map", false, p)) return rc;
     std::copy(p.cut->host_bucket_of.begin(), p.cut->host_bucket_of.end(), bucket_of);
     *n_groups = p.cut->n_groups;
     return 0;
@@ -2770,7 +2894,7 @@ extern "C" int rnad_bucket_map(const rnad_tree_t *tree, int64_t B, int32_t *buck
 extern "C" int rnad_bucket_shared_steps(const rnad_tree_t *tree, int64_t B, int32_t *n_shared) {
     RNAD_REQUIRE(tree && n_shared, "rnad_bucket_shared_steps: null argument");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_bucket_shared_steps: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_shared_steps", false, p)) return rc;
     std::vector<int32_t> path((size_t)p.cut->n_buckets);
     DeviceGuard guard(tree->device);
     RNAD_HIP_OK(hipMemcpy(path.data(), p.cut->bucket_path, path.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -2778,40 +2902,6 @@ extern "C" int rnad_bucket_shared_steps(const rnad_tree_t *tree, int64_t B, int3
         n_shared[b] = (path[(size_t)b] & (kSharedRoot - 1)) + ((b < p.cut->n_groups && (path[(size_t)b] & kSharedRoot)) ? 2 : 0);
     return 0;
 }
-
-namespace {
-// The compact rollout runs one workgroup per work item (k_bucket_rollout_items), the dense one a workgroup per kThreads columns: either
-// leaves one row of alive counts per workgroup.
-int64_t alive_rows(const rnad_tree_t *, int64_t B, const Plan &p, bool compact) { return compact ? p.max_items : (int64_t)blocks_for(B); }
-
-// REL = the type of a relative state under plan p
-#define RNAD_DISPATCH_REL(p_, ...)        \
-    if ((p_).rel_bytes == 1) {            \
-        using REL = uint8_t;              \
-        __VA_ARGS__;                      \
-    } else {                              \
-        using REL = uint16_t;             \
-        __VA_ARGS__;                      \
-    }
-int64_t alive_rows_max(int64_t B, const Plan &p) { return std::max<int64_t>(p.max_items, (int64_t)blocks_for(B)); }
-
-struct Scratch {
-    unsigned long long *decisions;  // [B]
-    int32_t *keys, *hist, *totals, *bucket_start, *alive_part;
-    float *policy;  // [2S][A]: the actor's policy per row when the caller hands logits
-};
-Scratch carve_scratch(void *ws, int64_t B, const Plan &p) {
-    Scratch s;
-    s.decisions = (unsigned long long *)ws;
-    s.keys = (int32_t *)(s.decisions + B);
-    s.hist = s.keys + B;
-    s.totals = s.hist + (int64_t)p.sort_blocks * p.cut->n_buckets;
-    s.bucket_start = s.totals + p.cut->n_buckets;
-    s.alive_part = s.bucket_start + p.cut->n_buckets;
-    s.policy = (float *)(((uintptr_t)(s.alive_part + alive_rows_max(B, p) * (kMaxSteps + 1)) + 15) & ~(uintptr_t)15);  // rows of (A + 3) & ~3 floats
-    return s;
-}
-}  // namespace
 
 namespace {
 __global__ void k_step_params_set(rnad_step_params_t *dst, uint64_t seed, float alpha, float one_minus_alpha) {
@@ -2883,30 +2973,29 @@ __global__ __launch_bounds__(kThreads) void k_clear_visited(int64_t rows, int64_
     }
 }
 
-struct RolloutBuffers {  // the dense trajectory (rnad_traj_t) or the compact one
-    int T_cap;
-    int64_t B;
-    void *indices;  // dense: int32 [T_cap + 1, B]; compact: the relative states, REL [T_cap + 1, B]
-    uint8_t *mask_bits;
-    float *policy;
-    int32_t *actions;
-    float *rewards, *values;
-    int32_t *alive;
-    unsigned long long *acts;  // compact: 3 bits per step
-    float *final_reward;       // compact
-    int32_t *visited;          // compact, optional: [2S] flags of the rows the batch went through
+// ---- what an entry point asks of rollout_bucketed_impl (RolloutRequest: the first six members are every caller's; of the rest an entry
+// point sets what it uses)
+struct ActorTable {  // the actor per (player, state) row: policy rows, or logits (the policy head then runs here, into Scratch::policy)
+    const float *table;
+    int64_t stride;
+    int is_policy;
 };
-
-// phases: 1 = keys + sort (needs the actor's rows of the upper states), 2 = the rollout in bucket order (needs the rows of every
-// non-empty group), 3 = both.  A caller that splits them (rnad_bucket_sort / rnad_bucket_play) evaluates its actor in stages:
-// the upper rows, then -- once the sort has shown which groups the batch descends into (group_flags) -- the rows of those groups.
-// play_rows / n_play_rows (phase 2 of a split call with a logits table): the rows that were evaluated for it.
-struct CountReps {  // where k_bucket_play_learn leaves the alive counts and the normalisers (behind the tickets of the accumulators)
-    double *norm_rep = nullptr;
-    int32_t *alive_rep = nullptr;
-    int T1 = 0;
-    int32_t *alive_out = nullptr;
-    double *norm_out = nullptr;
+struct LaneDraws {  // what the counter-based draws of a lane are keyed by
+    uint64_t seed;
+    int64_t lane0;
+    const rnad_step_params_t *device_params;
+};
+struct SortBuffers {  // the caller's buffers of the sort (sized by rnad_bucket_plan)
+    void *scratch;
+    int32_t *lane_ids, *items, *n_items;
+    double *norm;
+};
+struct CompactTraj {
+    void *states = nullptr;  // the relative states, REL [T_cap + 1, B]
+    int32_t *alive = nullptr;
+    unsigned long long *acts = nullptr;  // 3 bits per step
+    float *final_reward = nullptr;
+    int32_t *visited = nullptr;  // optional: [2S] flags of the rows the batch went through
 };
 struct FusedLearn {  // the learner of the batch in the rollout's launch (k_bucket_play_learn): what k_bucket_learn_c needs beyond the rollout's arguments
     const float *fast;
@@ -2915,258 +3004,352 @@ struct FusedLearn {  // the learner of the batch in the rollout's launch (k_buck
     bool distinct;  // the learner once per distinct trajectory of a work item (struct Distinct)
     const rnad_leaf_paths_t *leaf = nullptr;  // the learner on the tree's leaf paths, weighted with the lanes the rollout counted (two launches)
 };
+// phases: 1 = keys + sort (needs the actor's rows of the upper states), 2 = the rollout in bucket order (needs the rows of every
+// non-empty group), 3 = both.  A caller that splits them (rnad_bucket_sort / rnad_bucket_play) evaluates its actor in stages:
+// the upper rows, then -- once the sort has shown which groups the batch descends into (group_flags) -- the rows of those groups.
+// play_rows / n_play_rows (phase 2 of a split call with a logits table): the rows that were evaluated for it.
+struct RolloutRequest {
+    int T_cap;
+    int64_t B;
+    ActorTable actor;
+    LaneDraws draws;
+    SortBuffers sort;
+    hipStream_t stream;
+    int phases = 3;
+    const rnad_traj_t *dense = nullptr;  // the dense trajectory to fill; NULL: the compact one
+    CompactTraj out;
+    const float *value_table = nullptr;  // (dense)
+    int64_t value_stride = 1;
+    int32_t *group_flags = nullptr, *staged_rows = nullptr, *stage_rows0 = nullptr;  // (sort)
+    int64_t *n_staged = nullptr;
+    void *stage = nullptr;  // the stage buffer (carve_stage)
+    const int32_t *play_rows = nullptr;  // (play)
+    const int64_t *n_play_rows = nullptr;
+    bool visited_is_clear = false;  // the rnad_bucket_sort before this call cleared `visited`
+    KeysExpand expand;              // the copies of rnad_rows_expand the keys pass carries (rep_of NULL: none)
+    const FusedLearn *fused = nullptr;
+};
+
+// The copies an entry point asks the keys pass to carry, checked; `who` names it in the messages.
+int keys_expand_for(const char *who, const rnad_tree_t *tree, const int32_t *rep_of, int n_tables, float *const *tables,
+                    const int32_t *floats_per_row, KeysExpand &ex) {
+    ex.rep_of = rep_of;
+    ex.rows = 2 * tree->S;
+    ex.n = n_tables;
+    for (int k = 0; k < n_tables; ++k) {
+        RNAD_REQUIRE(tables[k] && floats_per_row[k] > 0 && floats_per_row[k] % 4 == 0 && ((uintptr_t)tables[k] & 15) == 0,
+                     "%s: table %d must be 16-byte aligned with a row of a multiple of 4 floats", who, k);
+        ex.tab[k] = reinterpret_cast<float4 *>(tables[k]);
+        ex.quads[k] = floats_per_row[k] / 4;
+        ex.max_quads = std::max(ex.max_quads, ex.quads[k]);
+    }
+    return 0;
+}
+
+// ---- the decisions of a call, each taken once
+// Which keys walk runs, and its dynamic LDS: all of the upper states' tables in LDS if they fit, else the top levels there and the
+// rest from the global tables (the hybrid walk), else the global tables.
+enum class KeysWalk { Lds, Hybrid, Global };
+struct KeysChoice {
+    KeysWalk walk;
+    size_t lds;
+};
+KeysChoice choose_keys_walk(const rnad_tree_t *tree, const Plan &p, const Switches &sw) {
+    const BucketCut &cut = *p.cut;
+    const bool walk_global = sw.keys_global.set && sw.keys_global.v != 0;  // (tests: the fallback on any tree)
+    const bool no_full_lds = sw.keys_lds.set && sw.keys_lds.v == 0;        // (tests: the hybrid walk on small trees)
+    const bool no_hybrid = sw.keys_hybrid.set && sw.keys_hybrid.v == 0;
+    const size_t full = keys_lds_bytes(cut.n_upper, cut.n_buckets, tree->A, tree->C);
+    if (cut.upper_walk && full <= kKeysLds && !walk_global && !no_full_lds) return {KeysWalk::Lds, full};
+    if (cut.upper_walk && cut.n_hot > 0 && cut.n_hot < cut.n_upper && !walk_global && !no_hybrid)
+        return {KeysWalk::Hybrid,
+                std::max(keys_hybrid_lds_bytes(cut.n_hot, cut.n_upper, tree->A, tree->C), (size_t)cut.n_buckets * sizeof(int32_t))};
+    return {KeysWalk::Global, 0};
+}
+
 // k_bucket_play_learn on the distinct trajectories of a work item (struct Distinct): larger items -- more lanes share a trajectory --
 // while the counters (a key per state of the group and outcome) and the list fit the LDS beside the learner's table.
 constexpr int kFusedChunkDefault = 512;      // (measured on configs[1]: 256 / 512 / 768 / 2048 lanes per item -> 0.181 / 0.171 / 0.171 / 0.177 ms per step)
 constexpr int kFusedLdsBudget = 26 * 1024;  // bytes of LDS per workgroup, the learner's table included: six workgroups to a CU
-int fused_distinct_keys(const rnad_tree_t *tree, const Plan &p, bool asked) {
+struct FusedPlan {
+    int chunk;          // lanes per work item: what the scatter cuts the buckets into and the play launch works through
+    int distinct_keys;  // counters of the distinct-trajectory learner; 0: the learner once per lane
+    size_t lds;         // dynamic LDS of the play launch
+};
+FusedPlan plan_fused(const rnad_tree_t *tree, const Plan &p, const Switches &sw, bool asked) {
     // opt-in (the caller's flag; RNAD_FUSED_DISTINCT=0 / 1 overrides it): the same sums bit for bit (tests/test_hip_bucket.py); what it buys
     // depends on how many lanes share a trajectory -- configs[1]: 4 % slower under the uniform policies of fresh nets, 6.5 % faster 5 000
     // updates later, 14 % after 30 000
-    if (const char *e = getenv("RNAD_FUSED_DISTINCT")) asked = atoi(e) != 0;
-    if (!asked) return 0;
-    return p.cut->rows * (tree->A * tree->A * tree->C + 1);
-}
-int fused_chunk(const rnad_tree_t *tree, const Plan &p, bool asked) {
-    int chunk = kFusedChunkDefault;
-    if (const char *e = getenv("RNAD_FUSED_CHUNK")) chunk = std::max(64, atoi(e));
-    chunk = std::max(chunk, p.chunk);
-    const int keys = fused_distinct_keys(tree, p, asked);
-    if (keys == 0 || (size_t)p.lds + ((size_t)keys + 2 + 2 * (size_t)chunk) * 4 > (size_t)kFusedLdsBudget) return p.chunk;  // (per lane, as played)
-    return chunk;
-}
-CountReps count_reps(const rnad_tree_t *tree, const Plan &p, void *accumulators, int T1, int32_t *alive_out, double *norm_out) {
-    const int64_t A1 = tree->A + 1;
-    unsigned long long *rep = (unsigned long long *)accumulators + 2 * tree->S * A1;
-    double *losses_raw = (double *)(rep + (int64_t)kReplicas * 2 * std::max(p.cut->n_upper, 1) * A1);
-    int32_t *overflow = (int32_t *)(losses_raw + 4);
-    CountReps c;
-    c.norm_rep = (double *)(overflow + 2 + kTicketGroups);  // (8-byte aligned: kTicketGroups is even)
-    c.alive_rep = (int32_t *)(c.norm_rep + 2 * kReplicas);
-    c.T1 = T1;
-    c.alive_out = alive_out;
-    c.norm_out = norm_out;
-    return c;
+    if (sw.fused_distinct.set) asked = sw.fused_distinct.v != 0;
+    const int keys = asked ? p.cut->rows * (tree->A * tree->A * tree->C + 1) : 0;
+    auto lds_with = [&](int chunk) { return (size_t)p.lds + ((size_t)keys + 2 + 2 * (size_t)chunk) * 4; };  // (per lane, as played)
+    FusedPlan f{p.chunk, 0, (size_t)p.lds};
+    if (keys == 0) return f;
+    const int chunk = std::max(sw.fused_chunk.set ? std::max(64, sw.fused_chunk.v) : kFusedChunkDefault, p.chunk);
+    if (lds_with(chunk) <= (size_t)kFusedLdsBudget) f.chunk = chunk;
+    // the distinct trajectories of the larger items -- and, with RNAD_FUSED_CHUNK set, of items of the plan's own chunk if those fit
+    if ((f.chunk > p.chunk || sw.fused_chunk.set) && lds_with(f.chunk) <= (size_t)kFusedLdsBudget) {
+        f.distinct_keys = keys;
+        f.lds = lds_with(f.chunk);
+    }
+    return f;
 }
 
-int finish_impl(const rnad_tree_t *tree, const Plan &p, const double *norm, const rnad_learn_params_t *hp, void *accumulators, double *losses,
-                float *dlogit_tab, float *dv_tab, const int32_t *rows, const int64_t *n_rows, const rnad_row_groups_t *groups,
-                hipStream_t stream, const CountReps *counts = nullptr);
+// ---- one rollout_bucketed_impl call.  Its launches are member functions: each names the values of the call as the driver does.
+struct RolloutCall {
+    const rnad_tree_t *tree;
+    const RolloutRequest &rq;
+    const Switches &sw;
+    const Plan &p;
+    const BucketCut &cut;
+    const Scratch s;
+    const StageOut stage;
+    const FusedPlan fplan;  // (rq.fused)
+    const int64_t B, S;
+    const int n_steps;  // env steps of the keys walk
+    const hipStream_t stream;
+    const uint64_t seed;
+    const int64_t lane0;
+    const rnad_step_params_t *device_params;
+    const float *policy_tab;  // the actor's policy rows: the caller's table, or Scratch::policy
+    int64_t policy_stride;
+    int vec4;
 
-int rollout_bucketed_impl(const rnad_tree_t *tree, const RolloutBuffers &tr, bool compact, const float *table, int64_t table_stride,
-                          int table_is_policy, const float *value_table, int64_t value_stride, uint64_t seed, int64_t lane0,
-                          const rnad_step_params_t *device_params, void *scratch, int32_t *lane_ids, int32_t *items, int32_t *n_items,
-                          double *norm, hipStream_t stream, int phases = 3, int32_t *group_flags = nullptr,
-                          const int32_t *play_rows = nullptr, const int64_t *n_play_rows = nullptr, int32_t *staged_rows = nullptr,
-                          int64_t *n_staged = nullptr, bool visited_is_clear = false, void *stage_buf = nullptr, int32_t *stage_rows0 = nullptr,
-                          const KeysExpand *expand = nullptr, const FusedLearn *fused = nullptr) {
-    Plan p;
-    RNAD_REQUIRE(make_plan(tree, tr.B, p), "rnad_rollout_bucketed: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
-    RNAD_REQUIRE_SIZED(tree, tr.B, p);
-    const int64_t B = tr.B, S = tree->S;
-    const Scratch s = carve_scratch(scratch, B, p);
-    const StageOut stage = carve_stage(stage_buf, B, S);
-    const int n_steps = std::min(p.cut->max_path, tr.T_cap), nb = p.cut->n_buckets;
-    ProfScope prof(PROF_ACT, stream);
-    const bool sort_phase = (phases & 1) != 0, play_phase = (phases & 2) != 0;
-    // `visited` is cleared by a kernel (memset nodes of captured graphs are not to be trusted, see learn_bucketed_impl): by the sort's last
-    // kernel when this call (or the rnad_bucket_sort before it, visited_is_clear) runs one, by a launch of its own otherwise
-    if (tr.visited && play_phase && !sort_phase && !visited_is_clear)
-        hipLaunchKernelGGL(k_clear_visited, dim3(blocks_for(2 * S, kThreads * 4)), dim3(kThreads), 0, stream, 2 * S, S, tr.visited);
-    const float *policy_tab = table;
-    int64_t policy_stride = table_stride;
-    if (!table_is_policy) {  // logits given: the policy head once per (player, state) row -- of the rows this phase can need
-        const uint8_t *mt = (const uint8_t *)tree->mask_tab;
-        if (phases == 3) {
-            RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_policy_rows<kA>), dim3(blocks_for(2 * S)), dim3(kThreads), 0, stream, 2 * S, table,
-                                                        table_stride, mt, s.policy, nullptr, nullptr, nullptr, 0, S));
-        } else if (sort_phase) {
-            const int nu = p.cut->n_upper;
-            RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_policy_rows<kA>), dim3(blocks_for(2 * ((int64_t)nu + 1))), dim3(kThreads), 0, stream,
-                                                        2 * S, table, table_stride, mt, s.policy, nullptr, nullptr,
-                                                        (const int32_t *)p.cut->upper_list, nu, S));
-        } else {
-            RNAD_REQUIRE(play_rows && n_play_rows, "rnad_bucket_play: a logits table needs the list of rows that were evaluated for it");
-            RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_policy_rows<kA>), dim3(blocks_for(2 * S)), dim3(kThreads), 0, stream, 2 * S, table,
-                                                        table_stride, mt, s.policy, play_rows, n_play_rows, nullptr, 0, S));
-        }
-        policy_tab = s.policy;
-        policy_stride = (tree->A + 3) & ~3;
+    template <int A, int TILE>
+    int keys_lds(size_t lds, const KeysExpand &ex) const {
+        return launch_lds(k_bucket_keys_lds<A, kPlayLds, TILE>, dim3(p.sort_blocks), dim3(kSortThreads), lds, stream, (const UpperWalk *)cut.upper_walk,
+                          (const int32_t *)cut.upper_list, cut.n_upper, cut.n_buckets, tree->C, S, B, n_steps, policy_tab, policy_stride,
+                          (int)cut.host_bucket_of[1], cut.n_groups, seed, device_params, lane0, s.keys, s.decisions, s.hist, rq.sort.norm, stage, ex);
     }
-    const int vec4 = (policy_stride % 4 == 0 && ((uintptr_t)policy_tab & 15) == 0) ? 1 : 0;
-    bool keys_with_hist = false;
-    if (sort_phase) {
-        ProfScope one(PROF_BUCKET_KEYS, stream);
-        const size_t keys_lds = keys_lds_bytes(p.cut->n_upper, nb, tree->A, tree->C);
-        const bool walk_global = getenv("RNAD_KEYS_GLOBAL") && atoi(getenv("RNAD_KEYS_GLOBAL")) != 0;  // (tests: the fallback on any tree)
-        const bool no_full_lds = getenv("RNAD_KEYS_LDS") && atoi(getenv("RNAD_KEYS_LDS")) == 0;  // (tests: the hybrid walk on small trees)
-        const bool use_lds = p.cut->upper_walk && keys_lds <= kKeysLds && !walk_global && !no_full_lds;
-        if (expand && !use_lds) {  // (only k_bucket_keys_lds carries the copies: a launch of their own in front of the other walks)
-            float *tabs[4];
-            int32_t widths[4];
-            for (int k = 0; k < expand->n; ++k) {
-                tabs[k] = reinterpret_cast<float *>(expand->tab[k]);
-                widths[k] = 4 * expand->quads[k];
-            }
-            if (int rc = rnad_rows_expand(expand->rows, expand->rep_of, expand->n, tabs, widths, stream)) return rc;
-            expand = nullptr;
-        }
-        if (use_lds) {  // the upper states' tables fit the LDS: walk there, one sort tile per workgroup
-            keys_with_hist = true;
-            if (keys_lds > 48 * 1024)
-                RNAD_DISPATCH_TILE(p, RNAD_DISPATCH_A(tree->A, RNAD_HIP_OK(hipFuncSetAttribute((const void *)k_bucket_keys_lds<kA, kPlayLds, kTile>,
-                                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)keys_lds))));
-            RNAD_DISPATCH_TILE(p, RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_bucket_keys_lds<kA, kPlayLds, kTile>), dim3(p.sort_blocks), dim3(kSortThreads), keys_lds, stream,
-                                                        (const UpperWalk *)p.cut->upper_walk, (const int32_t *)p.cut->upper_list, p.cut->n_upper, nb,
-                                                        tree->C, S, B, n_steps, policy_tab, policy_stride, (int)p.cut->host_bucket_of[1],
-                                                        p.cut->n_groups, seed, device_params, lane0, s.keys, s.decisions, s.hist, norm, stage,
-                                                        expand ? *expand : KeysExpand{})));
-            // (the copies themselves: workgroups of the scan launch below)
-        } else if (p.cut->upper_walk && p.cut->n_hot > 0 && p.cut->n_hot < p.cut->n_upper && !walk_global &&
-                   !(getenv("RNAD_KEYS_HYBRID") && atoi(getenv("RNAD_KEYS_HYBRID")) == 0)) {
-            // the top levels of the upper states in LDS, the rest from the global tables
-            const size_t hyb_lds = std::max(keys_hybrid_lds_bytes(p.cut->n_hot, p.cut->n_upper, tree->A, tree->C), (size_t)nb * sizeof(int32_t));
-            keys_with_hist = true;
-            if (hyb_lds > 48 * 1024)
-                RNAD_DISPATCH_TILE(p, RNAD_DISPATCH_A(tree->A, RNAD_HIP_OK(hipFuncSetAttribute((const void *)k_bucket_keys_hybrid<kA, kPlayLds, kTile>,
-                                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)hyb_lds))));
-            RNAD_DISPATCH_TILE(p, RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_bucket_keys_hybrid<kA, kPlayLds, kTile>), dim3(p.sort_blocks), dim3(kSortThreads), hyb_lds, stream,
-                                                        (const UpperWalk *)p.cut->upper_walk, (const int32_t *)p.cut->upper_list,
-                                                        (const int32_t *)p.cut->hot_list, (const int32_t *)p.cut->hot_of, p.cut->n_hot, p.cut->n_upper,
-                                                        tree->trans, (const int32_t *)p.cut->bucket_of, tree->C, S, B, n_steps, policy_tab, policy_stride,
-                                                        vec4, (int)p.cut->host_bucket_of[1], p.cut->n_groups, seed, device_params, lane0, s.keys,
-                                                        s.decisions, norm, stage, nb, s.hist)));
-        } else {
-            RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_bucket_keys<kA, kPlay>), dim3(blocks_for(B, kThreads * kPlay)), dim3(kThreads), 0, stream, tree->trans, tree->C,
-                                                        S, B, n_steps, policy_tab, policy_stride, vec4, (const int32_t *)p.cut->bucket_of,
-                                                        p.cut->n_groups, seed, device_params, lane0, s.keys, s.decisions, norm, stage));
-        }
+    template <int A, int TILE>
+    int keys_hybrid(size_t lds) const {
+        return launch_lds(k_bucket_keys_hybrid<A, kPlayLds, TILE>, dim3(p.sort_blocks), dim3(kSortThreads), lds, stream, (const UpperWalk *)cut.upper_walk,
+                          (const int32_t *)cut.upper_list, (const int32_t *)cut.hot_list, (const int32_t *)cut.hot_of, cut.n_hot, cut.n_upper,
+                          tree->trans, (const int32_t *)cut.bucket_of, tree->C, S, B, n_steps, policy_tab, policy_stride, vec4,
+                          (int)cut.host_bucket_of[1], cut.n_groups, seed, device_params, lane0, s.keys, s.decisions, rq.sort.norm, stage,
+                          cut.n_buckets, s.hist);
     }
-    const size_t lds = (size_t)nb * sizeof(int32_t);
-    if (sort_phase) {
-        ProfScope sort_passes(PROF_BUCKET_SORT, stream);
-        if (!keys_with_hist)
-            RNAD_DISPATCH_TILE(p, hipLaunchKernelGGL(k_bucket_hist<kTile>, dim3(p.sort_blocks), dim3(kSortThreads), lds, stream, B, nb, (const int32_t *)s.keys, s.hist));
+    template <int A>
+    void keys_global() const {
+        hipLaunchKernelGGL((k_bucket_keys<A, kPlay>), dim3(blocks_for(B, kThreads * kPlay)), dim3(kThreads), 0, stream, tree->trans, tree->C, S, B, n_steps,
+                           policy_tab, policy_stride, vec4, (const int32_t *)cut.bucket_of, cut.n_groups, seed, device_params, lane0, s.keys,
+                           s.decisions, rq.sort.norm, stage);
+    }
+    template <int A>
+    void rollout_dense() const {
+        const rnad_traj_t &tr = *rq.dense;
+        hipLaunchKernelGGL((k_bucket_rollout<A>), dim3(blocks_for(B)), dim3(kThreads), 0, stream, tree->trans, tree->C, S, B, rq.T_cap, policy_tab,
+                           policy_stride, rq.value_table, rq.value_stride, (const uint8_t *)tree->mask_tab, seed, device_params, lane0,
+                           (const int32_t *)rq.sort.lane_ids, (const unsigned long long *)s.decisions, tr.indices, tr.mask_bits, tr.policy, tr.actions,
+                           tr.rewards, tr.values, s.alive_part);
+    }
+    template <int A, class REL>
+    void rollout_items() const {
+        hipLaunchKernelGGL((k_bucket_rollout_items<A, REL, kRolloutLanes>), dim3((unsigned)p.max_items), dim3(kThreads / kRolloutLanes), 0, stream,
+                           tree->trans, tree->C, S, B, rq.T_cap, policy_tab, policy_stride, vec4, seed, device_params, lane0,
+                           (const int32_t *)rq.sort.lane_ids, (const unsigned long long *)s.decisions, (const Item *)rq.sort.items,
+                           (const int32_t *)rq.sort.n_items, (const int32_t *)cut.bucket_path, (const int32_t *)cut.bucket_lo,
+                           (const int32_t *)cut.path_states, std::max(cut.max_path, 1), cut.n_groups, (REL *)rq.out.states, s.alive_part, rq.out.acts,
+                           rq.out.final_reward, rq.out.visited);
+    }
+    // every work item's workgroup plays its lanes and adds up their update
+    template <int A, class REL>
+    int play_learn(const Accumulators &acc, const FixedPoint &fx) const {
+        auto kern = fplan.distinct_keys > 0 ? k_bucket_play_learn<A, REL, true> : k_bucket_play_learn<A, REL, false>;
+        return launch_lds(kern, dim3((unsigned)p.max_items), dim3(kThreads), fplan.lds, stream, tree->trans, tree->C, S, B, rq.T_cap, policy_tab,
+                          policy_stride, vec4, seed, device_params, lane0, (const int32_t *)rq.sort.lane_ids, (const unsigned long long *)s.decisions,
+                          (const Item *)rq.sort.items, (const int32_t *)rq.sort.n_items, (const int32_t *)cut.bucket_path,
+                          (const int32_t *)cut.bucket_lo, (const int32_t *)cut.path_states, std::max(cut.max_path, 1), cut.n_groups,
+                          (REL *)rq.out.states, acc.alive_rep, acc.norm_rep, rq.out.acts, rq.out.final_reward, cut.rows, p.path_words,
+                          std::max(cut.n_upper, 1), (const int32_t *)cut.bucket_of, rq.fused->fast, *rq.fused->hp, fx, acc.acc, acc.rep, acc.overflow,
+                          p.lds / 8, fplan.distinct_keys, fplan.chunk);
+    }
+    // rollout (lanes counted per terminal transition), then the learner on the leaf paths of the tree: n_cols columns whatever the batch --
+    // and none of the per-lane learner's work for lanes that share a trajectory
+    template <int A, class REL>
+    int play_count(const Accumulators &acc, const FixedPoint &fx, const LeafCount &lcount) const {
+        const rnad_leaf_paths_t &lf = *rq.fused->leaf;
+        hipLaunchKernelGGL((k_bucket_play_count<A, REL>), dim3((unsigned)p.max_items), dim3(kThreads), 0, stream, tree->trans, tree->C, S, B, rq.T_cap,
+                           policy_tab, policy_stride, vec4, seed, device_params, lane0, (const int32_t *)rq.sort.lane_ids,
+                           (const unsigned long long *)s.decisions, (const Item *)rq.sort.items, (const int32_t *)rq.sort.n_items,
+                           (const int32_t *)cut.bucket_path, (const int32_t *)cut.bucket_lo, (const int32_t *)cut.path_states,
+                           std::max(cut.max_path, 1), cut.n_groups, (REL *)rq.out.states, acc.alive_rep, acc.norm_rep, rq.out.acts,
+                           rq.out.final_reward, lf.col_of, s.keys, lcount);
+        return launch_lds(k_bucket_learn_c<A, REL, false, true>, dim3((unsigned)lf.max_items + 7), dim3(kThreads), (size_t)p.lds, stream, rq.T_cap,
+                          lf.n_cols, S, cut.rows, p.path_words, cut.n_groups, std::max(cut.n_upper, 1), (const Item *)lf.items, lf.n_items,
+                          (const int32_t *)cut.bucket_of, (const int32_t *)cut.bucket_lo, (const int32_t *)cut.bucket_path,
+                          (const int32_t *)cut.path_states, std::max(cut.max_path, 1), (const REL *)lf.states, rq.fused->fast,
+                          (const unsigned long long *)lf.acts, lf.final_reward, (const float *)nullptr, *rq.fused->hp, fx, acc.acc, acc.rep,
+                          (double *)nullptr, acc.overflow, (const int32_t *)nullptr, 0, rq.T_cap + 1, (int32_t *)nullptr, (double *)nullptr,
+                          (const int32_t *)s.keys, (const int32_t *)s.bucket_start, (const int32_t *)s.totals, lcount);
+    }
+
+    // keys, then the stable counting sort of the lanes by key and the work items
+    int sort_lanes() const {
+        const int nb = cut.n_buckets;
+        const KeysChoice keys = choose_keys_walk(tree, p, sw);
+        bool copies = rq.expand.rep_of != nullptr;  // rows to copy that a launch below still has to carry
         {
-            const int scan_blocks = (nb + kScanCols - 1) / kScanCols;
-            int copy_blocks = 0;
-            if (expand) {  // a thread per (row, 16-byte chunk) and pass; two passes per thread keep the launch at a few hundred workgroups
-                copy_blocks = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (expand->rows * expand->max_quads + 2 * kSortThreads - 1) / (2 * kSortThreads)));
-                if (const char *e = getenv("RNAD_EXPAND_BLOCKS")) copy_blocks = std::max(1, atoi(e));  // tuning knob
+            ProfScope one(PROF_BUCKET_KEYS, stream);
+            if (copies && keys.walk != KeysWalk::Lds) {  // (only k_bucket_keys_lds carries the copies: a launch of their own in front of the other walks)
+                float *tabs[4];
+                int32_t widths[4];
+                for (int k = 0; k < rq.expand.n; ++k) {
+                    tabs[k] = reinterpret_cast<float *>(rq.expand.tab[k]);
+                    widths[k] = 4 * rq.expand.quads[k];
+                }
+                if (int rc = rnad_rows_expand(rq.expand.rows, rq.expand.rep_of, rq.expand.n, tabs, widths, stream)) return rc;
+                copies = false;
             }
-            hipLaunchKernelGGL(k_bucket_scan, dim3(scan_blocks + copy_blocks), dim3(kSortThreads), 0, stream, p.sort_blocks, nb, s.hist, s.totals,
-                               scan_blocks, expand ? *expand : KeysExpand{});
-            expand = nullptr;  // (done)
+            if (keys.walk == KeysWalk::Lds) {  // one sort tile per workgroup (the copies themselves: workgroups of the scan launch below)
+                RNAD_DISPATCH_TILE(p, RNAD_DISPATCH_A(tree->A, if (int rc = keys_lds<kA, kTile>(keys.lds, copies ? rq.expand : KeysExpand{})) return rc));
+            } else if (keys.walk == KeysWalk::Hybrid) {
+                RNAD_DISPATCH_TILE(p, RNAD_DISPATCH_A(tree->A, if (int rc = keys_hybrid<kA, kTile>(keys.lds)) return rc));
+            } else {
+                RNAD_DISPATCH_A(tree->A, keys_global<kA>());
+            }
         }
+        ProfScope sort_passes(PROF_BUCKET_SORT, stream);
+        if (keys.walk == KeysWalk::Global)  // (the walks in LDS count their tile's lanes per bucket themselves)
+            RNAD_DISPATCH_TILE(p, hipLaunchKernelGGL(k_bucket_hist<kTile>, dim3(p.sort_blocks), dim3(kSortThreads), (size_t)nb * sizeof(int32_t), stream, B, nb,
+                                                     (const int32_t *)s.keys, s.hist));
+        const int scan_blocks = (nb + kScanCols - 1) / kScanCols;
+        int copy_blocks = 0;
+        if (copies) {  // a thread per (row, 16-byte chunk) and pass; two passes per thread keep the launch at a few hundred workgroups
+            copy_blocks = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (rq.expand.rows * rq.expand.max_quads + 2 * kSortThreads - 1) / (2 * kSortThreads)));
+            if (sw.expand_blocks.set) copy_blocks = std::max(1, sw.expand_blocks.v);  // tuning knob
+        }
+        hipLaunchKernelGGL(k_bucket_scan, dim3(scan_blocks + copy_blocks), dim3(kSortThreads), 0, stream, p.sort_blocks, nb, s.hist, s.totals, scan_blocks,
+                           copies ? rq.expand : KeysExpand{});
         // bucket_start | first item of every bucket | as many counter rows as fit the LDS (16 waves share them in turns)
         int wave_rows = 16;
         while (wave_rows > 1 && ((2 + wave_rows) * (size_t)nb + 1) * sizeof(int32_t) > kKeysLds) wave_rows >>= 1;
-        if (const char *force = getenv("RNAD_SCATTER_ROWS")) wave_rows = std::max(1, std::min(wave_rows, atoi(force)));  // tuning knob
+        if (sw.scatter_rows.set) wave_rows = std::max(1, std::min(wave_rows, sw.scatter_rows.v));  // tuning knob
         const size_t scatter_lds = ((2 + wave_rows) * (size_t)nb + 1) * sizeof(int32_t);
         RNAD_REQUIRE(scatter_lds <= 160 * 1024, "rnad_bucket_sort: %d buckets do not fit the sort's LDS", nb);
-        if (scatter_lds > 48 * 1024)
-            RNAD_DISPATCH_TILE(p, RNAD_HIP_OK(hipFuncSetAttribute((const void *)k_bucket_scatter<kTile>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds)));
-        RNAD_DISPATCH_TILE(p, hipLaunchKernelGGL(k_bucket_scatter<kTile>, dim3(p.sort_blocks), dim3(kSortThreads), scatter_lds, stream, B, nb, (const int32_t *)s.keys,
-                           (const int32_t *)s.hist, (const int32_t *)s.totals, fused ? fused_chunk(tree, p, fused->distinct) : p.chunk, (Item *)items, n_items, lane_ids, wave_rows, S,
-                           p.cut->n_groups, (const int32_t *)p.cut->bucket_lo, (const int32_t *)p.cut->bucket_span,
-                           (const int32_t *)p.cut->group_by_lo, staged_rows, n_staged, tr.visited, (const uint32_t *)stage.root, stage.sorted,
-                           (const uint32_t *)stage.mark0, stage.root ? stage_rows0 : nullptr, stage.counts, seed, device_params, s.bucket_start));
-        if (group_flags)
-            hipLaunchKernelGGL(k_group_flags, dim3(blocks_for(S)), dim3(kThreads), 0, stream, S, (const int32_t *)p.cut->bucket_of,
-                               p.cut->n_groups, (const int32_t *)s.totals, group_flags);
+        RNAD_DISPATCH_TILE(p, if (int rc = launch_lds(k_bucket_scatter<kTile>, dim3(p.sort_blocks), dim3(kSortThreads), scatter_lds, stream, B, nb,
+                                                      (const int32_t *)s.keys, (const int32_t *)s.hist, (const int32_t *)s.totals, fplan.chunk,
+                                                      (Item *)rq.sort.items, rq.sort.n_items, rq.sort.lane_ids, wave_rows, S, cut.n_groups,
+                                                      (const int32_t *)cut.bucket_lo, (const int32_t *)cut.bucket_span, (const int32_t *)cut.group_by_lo,
+                                                      rq.staged_rows, rq.n_staged, rq.out.visited, (const uint32_t *)stage.root, stage.sorted,
+                                                      (const uint32_t *)stage.mark0, stage.root ? rq.stage_rows0 : nullptr, stage.counts, seed,
+                                                      device_params, s.bucket_start)) return rc);
+        if (rq.group_flags)
+            hipLaunchKernelGGL(k_group_flags, dim3(blocks_for(S)), dim3(kThreads), 0, stream, S, (const int32_t *)cut.bucket_of, cut.n_groups,
+                               (const int32_t *)s.totals, rq.group_flags);
+        return 0;
     }
+
+    // the rollout in bucket order
+    int play_lanes() const {
+        const FusedLearn *fused = rq.fused;
+        ProfScope one(fused ? PROF_BUCKET_LEARN : PROF_BUCKET_ROLLOUT, stream);  // (k_bucket_play_learn is booked as the learner: the larger share)
+        if (rq.dense) {
+            RNAD_DISPATCH_A(tree->A, rollout_dense<kA>());
+            return 0;
+        }
+        RNAD_REQUIRE(rq.sort.items && rq.sort.n_items, "rnad_rollout_bucketed_compact: the work list of the sort is needed to play");
+        if (!fused) {
+            RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, rollout_items<kA, REL>()));
+            return 0;
+        }
+        const Accumulators acc = carve_accumulators(fused->accumulators, tree, p);
+        const FixedPoint fx = fixed_point_for(*fused->hp);
+        RNAD_REQUIRE(!fx.check_l, "rnad_rollout_learn_bucketed_compact: a NeuRD clip of 2^29 or more takes the two-launch path");
+        RNAD_REQUIRE(!rq.out.visited, "rnad_rollout_learn_bucketed_compact: no visited flags (lazy rows evaluate their records after the rollout)");
+        if (!fused->leaf) {
+            RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, if (int rc = play_learn<kA, REL>(acc, fx)) return rc));
+            return 0;
+        }
+        const rnad_leaf_paths_t &lf = *fused->leaf;
+        RNAD_REQUIRE(lf.n_cols >= 1 && lf.states && lf.acts && lf.final_reward && lf.items && lf.n_items && lf.col_of && lf.max_items >= 1,
+                     "rnad_rollout_learn_bucketed_compact: incomplete rnad_leaf_paths_t");
+        RNAD_REQUIRE(lf.rows == cut.rows && lf.T_cap == rq.T_cap && rq.T_cap == 2 * tree->max_depth,
+                     "rnad_rollout_learn_bucketed_compact: the leaf paths were built for another cut / window (rows %d vs %d, T_cap %d vs %d, "
+                     "2 * depth %d)", lf.rows, cut.rows, lf.T_cap, rq.T_cap, 2 * tree->max_depth);
+        LeafCount lcount;
+        if (lf.col_count && lf.bucket_col0 && lf.crowded_lanes > 0)
+            lcount = LeafCount{lf.col_count, lf.bucket_col0, (const int32_t *)s.totals, lf.crowded_lanes};
+        RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, if (int rc = play_count<kA, REL>(acc, fx, lcount)) return rc));
+        return 0;
+    }
+};
+
+int rollout_bucketed_impl(const rnad_tree_t *tree, const Switches &sw, const RolloutRequest &rq) {
+    Plan p;
+    if (int rc = plan_for(tree, rq.B, sw, "rnad_rollout_bucketed", true, p)) return rc;
+    const int64_t B = rq.B, S = tree->S;
+    const hipStream_t stream = rq.stream;
+    RolloutCall c{tree, rq, sw, p, *p.cut, carve_scratch(rq.sort.scratch, tree, B, p), carve_stage(rq.stage, B, S),
+                  rq.fused ? plan_fused(tree, p, sw, rq.fused->distinct) : FusedPlan{p.chunk, 0, (size_t)p.lds}, B, S,
+                  std::min(p.cut->max_path, rq.T_cap), stream, rq.draws.seed, rq.draws.lane0, rq.draws.device_params, rq.actor.table, rq.actor.stride, 0};
+    ProfScope prof(PROF_ACT, stream);
+    const bool sort_phase = (rq.phases & 1) != 0, play_phase = (rq.phases & 2) != 0;
+    // `visited` is cleared by a kernel (memset nodes of captured graphs are not to be trusted, see learn_bucketed_impl): by the sort's last
+    // kernel when this call (or the rnad_bucket_sort before it, visited_is_clear) runs one, by a launch of its own otherwise
+    if (rq.out.visited && play_phase && !sort_phase && !rq.visited_is_clear)
+        hipLaunchKernelGGL(k_clear_visited, dim3(blocks_for(2 * S, kThreads * 4)), dim3(kThreads), 0, stream, 2 * S, S, rq.out.visited);
+    if (!rq.actor.is_policy) {  // logits given: the policy head once per (player, state) row -- of the rows this phase can need:
+        // both phases: every row; the sort alone: the rows of the upper states; the play alone: the rows the caller lists
+        const bool upper = rq.phases == 1, listed = rq.phases == 2;
+        const int nu = upper ? p.cut->n_upper : 0;
+        RNAD_REQUIRE(!listed || (rq.play_rows && rq.n_play_rows), "rnad_bucket_play: a logits table needs the list of rows that were evaluated for it");
+        RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_policy_rows<kA>), dim3(blocks_for(upper ? 2 * ((int64_t)nu + 1) : 2 * S)), dim3(kThreads), 0, stream,
+                                                    2 * S, rq.actor.table, rq.actor.stride, (const uint8_t *)tree->mask_tab, c.s.policy,
+                                                    listed ? rq.play_rows : nullptr, listed ? rq.n_play_rows : nullptr,
+                                                    upper ? (const int32_t *)p.cut->upper_list : nullptr, nu, S));
+        c.policy_tab = c.s.policy;
+        c.policy_stride = (tree->A + 3) & ~3;
+    }
+    c.vec4 = (c.policy_stride % 4 == 0 && ((uintptr_t)c.policy_tab & 15) == 0) ? 1 : 0;
+    if (sort_phase)
+        if (int rc = c.sort_lanes()) return rc;
     RNAD_HIP_OK(hipGetLastError());
     if (!play_phase) return 0;
-    const unsigned grid = blocks_for(B);
-    int alive_n = (int)grid;  // rows of alive_part the rollout kernel leaves
-    {
-        ProfScope one(fused ? PROF_BUCKET_LEARN : PROF_BUCKET_ROLLOUT, stream);  // (k_bucket_play_learn is booked as the learner: the larger share)
-#define RNAD_BUCKET_ROLLOUT()                                                                                                            \
-    hipLaunchKernelGGL((k_bucket_rollout<kA>), dim3(grid), dim3(kThreads), 0, stream, tree->trans, tree->C, S, B, tr.T_cap, policy_tab,     \
-                       policy_stride, value_table, value_stride, (const uint8_t *)tree->mask_tab, seed, device_params, lane0,               \
-                       (const int32_t *)lane_ids, (const unsigned long long *)s.decisions, (int32_t *)tr.indices, tr.mask_bits, tr.policy, tr.actions, \
-                       tr.rewards, tr.values, s.alive_part)
-        if (compact) {
-            RNAD_REQUIRE(items && n_items, "rnad_rollout_bucketed_compact: the work list of the sort is needed to play");
-            alive_n = (int)p.max_items;
-            if (fused) {
-                const int64_t A1 = tree->A + 1;
-                unsigned long long *acc = (unsigned long long *)fused->accumulators;
-                unsigned long long *rep = acc + 2 * S * A1;
-                const int nu = p.cut->n_upper;
-                double *losses_raw = (double *)(rep + (int64_t)kReplicas * 2 * std::max(nu, 1) * A1);
-                int32_t *overflow = (int32_t *)(losses_raw + 4);
-                const FixedPoint fx = fixed_point_for(*fused->hp);
-                const CountReps cr = count_reps(tree, p, fused->accumulators, tr.T_cap + 1, nullptr, nullptr);
-                RNAD_REQUIRE(!fx.check_l, "rnad_rollout_learn_bucketed_compact: a NeuRD clip of 2^29 or more takes the two-launch path");
-                RNAD_REQUIRE(!tr.visited, "rnad_rollout_learn_bucketed_compact: no visited flags (lazy rows evaluate their records after the rollout)");
-                const int f_chunk = fused_chunk(tree, p, fused->distinct);
-                const int d_keys = f_chunk > p.chunk || getenv("RNAD_FUSED_CHUNK") ? fused_distinct_keys(tree, p, fused->distinct) : 0;
-                const int d_keys_fit = (size_t)p.lds + ((size_t)d_keys + 2 + 2 * (size_t)f_chunk) * 4 <= (size_t)kFusedLdsBudget ? d_keys : 0;
-                const size_t f_lds = (size_t)p.lds + (d_keys_fit ? ((size_t)d_keys_fit + 2 + 2 * (size_t)f_chunk) * 4 : 0);
-#define RNAD_PLAY_LEARN()                                                                                                              \
-    do {                                                                                                                               \
-        auto kern = d_keys_fit > 0 ? k_bucket_play_learn<kA, REL, true> : k_bucket_play_learn<kA, REL, false>;                         \
-        if (f_lds > 48 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f_lds)); \
-        hipLaunchKernelGGL(kern, dim3((unsigned)p.max_items), dim3(kThreads), f_lds, stream, tree->trans, tree->C, S, B, tr.T_cap,     \
-                           policy_tab, policy_stride, vec4, seed, device_params, lane0, (const int32_t *)lane_ids,                     \
-                           (const unsigned long long *)s.decisions, (const Item *)items, (const int32_t *)n_items,                     \
-                           (const int32_t *)p.cut->bucket_path, (const int32_t *)p.cut->bucket_lo, (const int32_t *)p.cut->path_states, \
-                           std::max(p.cut->max_path, 1), p.cut->n_groups, (REL *)tr.indices, cr.alive_rep, cr.norm_rep, tr.acts,       \
-                           tr.final_reward, p.cut->rows, p.path_words, std::max(nu, 1), (const int32_t *)p.cut->bucket_of, fused->fast, *fused->hp, fx, \
-                           acc, rep, overflow, p.lds / 8, d_keys_fit, f_chunk);                                                        \
-    } while (0)
-                if (fused->leaf) {
-                    // rollout (lanes counted per terminal transition), then the learner on the leaf paths of the tree: n_cols columns whatever
-                    // the batch -- and none of the per-lane learner's work for lanes that share a trajectory
-                    const rnad_leaf_paths_t &lf = *fused->leaf;
-                    RNAD_REQUIRE(lf.n_cols >= 1 && lf.states && lf.acts && lf.final_reward && lf.items && lf.n_items && lf.col_of && lf.max_items >= 1,
-                                 "rnad_rollout_learn_bucketed_compact: incomplete rnad_leaf_paths_t");
-                    RNAD_REQUIRE(lf.rows == p.cut->rows && lf.T_cap == tr.T_cap && tr.T_cap == 2 * tree->max_depth,
-                                 "rnad_rollout_learn_bucketed_compact: the leaf paths were built for another cut / window (rows %d vs %d, T_cap %d vs %d, "
-                                 "2 * depth %d)", lf.rows, p.cut->rows, lf.T_cap, tr.T_cap, 2 * tree->max_depth);
-#define RNAD_PLAY_COUNT()                                                                                                              \
-    do {                                                                                                                               \
-        hipLaunchKernelGGL((k_bucket_play_count<kA, REL>), dim3((unsigned)p.max_items), dim3(kThreads), 0, stream, tree->trans, tree->C, S, B,   \
-                           tr.T_cap, policy_tab, policy_stride, vec4, seed, device_params, lane0, (const int32_t *)lane_ids,          \
-                           (const unsigned long long *)s.decisions, (const Item *)items, (const int32_t *)n_items,                     \
-                           (const int32_t *)p.cut->bucket_path, (const int32_t *)p.cut->bucket_lo, (const int32_t *)p.cut->path_states, \
-                           std::max(p.cut->max_path, 1), p.cut->n_groups, (REL *)tr.indices, cr.alive_rep, cr.norm_rep, tr.acts,       \
-                           tr.final_reward, lf.col_of, s.keys, lcount);                                                                \
-        auto kern = k_bucket_learn_c<kA, REL, false, true>;                                                                           \
-        if (p.lds > 48 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds)); \
-        hipLaunchKernelGGL(kern, dim3((unsigned)lf.max_items + 7), dim3(kThreads), (size_t)p.lds, stream, tr.T_cap, lf.n_cols, S, p.cut->rows,  \
-                           p.path_words, p.cut->n_groups, std::max(nu, 1), (const Item *)lf.items, lf.n_items,                        \
-                           (const int32_t *)p.cut->bucket_of, (const int32_t *)p.cut->bucket_lo, (const int32_t *)p.cut->bucket_path,  \
-                           (const int32_t *)p.cut->path_states, std::max(p.cut->max_path, 1), (const REL *)lf.states, fused->fast,     \
-                           (const unsigned long long *)lf.acts, lf.final_reward, (const float *)nullptr, *fused->hp, fx, acc, rep,     \
-                           (double *)nullptr, overflow, (const int32_t *)nullptr, 0, tr.T_cap + 1, (int32_t *)nullptr, (double *)nullptr, \
-                           (const int32_t *)s.keys, (const int32_t *)s.bucket_start, (const int32_t *)s.totals, lcount);               \
-    } while (0)
-                    LeafCount lcount;
-                    if (lf.col_count && lf.bucket_col0 && lf.crowded_lanes > 0)
-                        lcount = LeafCount{lf.col_count, lf.bucket_col0, (const int32_t *)s.totals, lf.crowded_lanes};
-                    RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, RNAD_PLAY_COUNT()));
-#undef RNAD_PLAY_COUNT
-                } else
-                RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, RNAD_PLAY_LEARN()));
-#undef RNAD_PLAY_LEARN
-            } else
-            RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL(
-                                     (k_bucket_rollout_items<kA, REL, kRolloutLanes>), dim3((unsigned)p.max_items), dim3(kThreads / kRolloutLanes), 0, stream, tree->trans, tree->C,
-                                     S, B, tr.T_cap, policy_tab, policy_stride, vec4, seed, device_params, lane0, (const int32_t *)lane_ids,
-                                     (const unsigned long long *)s.decisions, (const Item *)items, (const int32_t *)n_items,
-                                     (const int32_t *)p.cut->bucket_path, (const int32_t *)p.cut->bucket_lo, (const int32_t *)p.cut->path_states,
-                                     std::max(p.cut->max_path, 1), p.cut->n_groups, (REL *)tr.indices, s.alive_part, tr.acts, tr.final_reward,
-                                     tr.visited)));
-        } else {
-            RNAD_DISPATCH_A(tree->A, RNAD_BUCKET_ROLLOUT());
-        }
-#undef RNAD_BUCKET_ROLLOUT
-    }
-    if (tr.alive && !fused)  // (NULL: the caller lets rnad_learn_bucketed_compact add the counts up, or calls rnad_bucket_alive)
-        hipLaunchKernelGGL(k_bucket_alive, dim3(tr.T_cap + 1), dim3(kThreads), 0, stream, alive_n, tr.T_cap + 1, (const int32_t *)s.alive_part,
-                           tr.alive, norm);
+    if (int rc = c.play_lanes()) return rc;
+    int32_t *alive = rq.dense ? rq.dense->alive : rq.out.alive;
+    if (alive && !rq.fused)  // (NULL: the caller lets rnad_learn_bucketed_compact add the counts up, or calls rnad_bucket_alive)
+        hipLaunchKernelGGL(k_bucket_alive, dim3(rq.T_cap + 1), dim3(kThreads), 0, stream, (int)alive_rows(B, p, !rq.dense), rq.T_cap + 1,
+                           (const int32_t *)c.s.alive_part, alive, rq.sort.norm);
+    RNAD_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// upper rows out of their replicas, then sums -> normalised fp32 tables (and the two logged losses)
+struct FinishOut {
+    double *losses;
+    float *dlogit_tab, *dv_tab;
+    const int32_t *rows = nullptr;  // the rows to finish (NULL: all) ...
+    const int64_t *n_rows = nullptr;
+    const rnad_row_groups_t *groups = nullptr;  // ... and the groups of rows that share an observation
+};
+struct Counts {  // the alive counts and normalisers k_bucket_play_learn left in the accumulators: k_bucket_finish adds them up as well
+    int T1;
+    int32_t *alive_out;
+    double *norm_out;
+};
+int finish_impl(const rnad_tree_t *tree, const Plan &p, const Accumulators &acc, const double *norm, const rnad_learn_params_t *hp,
+                const FinishOut &out, hipStream_t stream, const Counts *counts = nullptr) {
+    const int64_t S = tree->S;
+    const int nu = p.cut->n_upper;
+    const rnad_row_groups_t *groups = out.groups;
+    const FixedPoint fx = fixed_point_for(*hp);
+    const int n_multi = groups ? groups->n_groups : 0;
+    RNAD_REQUIRE(n_multi >= 0 && (n_multi == 0 || (groups->start && groups->order && out.rows)),
+                 "rnad_bucket_finish: row groups come with their start / order arrays and with the list of the rows outside them");
+    ProfScope fin(PROF_BUCKET_FINISH, stream);
+    const unsigned row_blocks = std::min(blocks_for(2 * S, kThreads * kFinishRows), 512u), upper_blocks = nu > 0 ? blocks_for(2 * (int64_t)nu, kThreads / 64) : 0;
+    const unsigned group_blocks = n_multi > 0 ? blocks_for(n_multi, kThreads / 64) : 0;
+    RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_bucket_finish<kA>), dim3(row_blocks + upper_blocks + group_blocks), dim3(kThreads), 0, stream, S,
+                                                (int)row_blocks, out.rows, out.n_rows, nu, p.cut->n_groups, (const int32_t *)p.cut->upper_list,
+                                                (const int32_t *)p.cut->bucket_of, acc.acc, acc.rep, norm, hp->w_v, hp->w_n, fx, acc.overflow,
+                                                acc.losses_raw, out.losses, out.dlogit_tab, out.dv_tab, (int)upper_blocks, n_multi,
+                                                n_multi ? groups->start : (const int32_t *)nullptr,
+                                                n_multi ? groups->order : (const int32_t *)nullptr,
+                                                n_multi ? groups->first : (const int32_t *)nullptr, (groups && out.rows) ? groups->rows_below_cut : 0,
+                                                counts ? acc.alive_rep : (int32_t *)nullptr, counts ? acc.norm_rep : (double *)nullptr,
+                                                counts ? counts->T1 : 0, counts ? counts->alive_out : (int32_t *)nullptr,
+                                                counts ? counts->norm_out : (double *)nullptr));
     RNAD_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -3181,24 +3364,31 @@ extern "C" int rnad_bucket_sort(const rnad_tree_t *tree, int T_cap, int64_t B, c
     RNAD_REQUIRE(!staged_rows == !n_staged, "rnad_bucket_sort: staged_rows and n_staged go together");
     RNAD_REQUIRE(T_cap >= 1 && T_cap <= kCompactSteps && B >= 1, "rnad_bucket_sort: 1 <= T_cap <= %d, got %d", kCompactSteps, T_cap);
     RNAD_REQUIRE(table_stride >= tree->A, "rnad_bucket_sort: bad table stride");
-    const RolloutBuffers out{T_cap, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, visited};
-    return rollout_bucketed_impl(tree, out, true, table, table_stride, table_is_policy, nullptr, 1, seed, lane0, device_params, scratch,
-                                 lane_ids, items, n_items, norm, (hipStream_t)stream, 1, group_flags, nullptr, nullptr, staged_rows, n_staged,
-                                 false, stage, stage_rows0);
+    RolloutRequest rq{T_cap, B, {table, table_stride, table_is_policy}, {seed, lane0, device_params}, {scratch, lane_ids, items, n_items, norm},
+                      (hipStream_t)stream};
+    rq.phases = 1;
+    rq.out.visited = visited;
+    rq.group_flags = group_flags;
+    rq.staged_rows = staged_rows;
+    rq.n_staged = n_staged;
+    rq.stage = stage;
+    rq.stage_rows0 = stage_rows0;
+    return rollout_bucketed_impl(tree, read_switches(), rq);
 }
 
 extern "C" int64_t rnad_bucket_stage_bytes(const rnad_tree_t *tree, int64_t B) {
     if (!tree || B < 1) return -1;
     if (tree->S > ((int64_t)1 << kStageRootBits)) return -1;  // (a root word holds the state in 26 bits)
-    return (int64_t)(2 * sizeof(unsigned long long) + 2 * (size_t)B * sizeof(uint32_t) + 2 * (size_t)tree->S * sizeof(uint32_t));
+    int64_t bytes = 0;
+    carve_stage(nullptr, B, tree->S, &bytes);
+    return bytes;
 }
 
 extern "C" int rnad_bucket_stage_rows(const rnad_tree_t *tree, int64_t B, int level, uint64_t seed, const rnad_step_params_t *device_params,
                                       void *stage, int32_t *rows, void *stream) {
     RNAD_REQUIRE(tree && stage && rows && (level == 0 || level == 1), "rnad_bucket_stage_rows: null argument / level must be 0 or 1");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_bucket_stage_rows: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
-    RNAD_REQUIRE_SIZED(tree, B, p);
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_stage_rows", true, p)) return rc;
     const StageOut st = carve_stage(stage, B, tree->S);
     if (level == 0)
         hipLaunchKernelGGL(k_stage_rows<0>, dim3(blocks_for(tree->S, kSortThreads * kStagePer)), dim3(kSortThreads), 0, (hipStream_t)stream, tree->S, (const uint32_t *)st.mark0,
@@ -3216,8 +3406,7 @@ extern "C" int rnad_bucket_stage_walk(const rnad_tree_t *tree, int T_cap, int64_
     RNAD_REQUIRE(tree && policy_rows && scratch && stage && lane_ids, "rnad_bucket_stage_walk: null argument");
     RNAD_REQUIRE(stride >= tree->A && T_cap >= 1, "rnad_bucket_stage_walk: bad table stride / T_cap");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_bucket_stage_walk: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
-    RNAD_REQUIRE_SIZED(tree, B, p);
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_stage_walk", true, p)) return rc;
     const StageOut st = carve_stage(stage, B, tree->S);
     const int vec4 = (stride % 4 == 0 && ((uintptr_t)policy_rows & 15) == 0) ? 1 : 0;
     RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_stage_walk<kA>), dim3(blocks_for(B)), dim3(kThreads), 0, (hipStream_t)stream, tree->trans, tree->C,
@@ -3232,25 +3421,26 @@ extern "C" int rnad_bucket_play(const rnad_tree_t *tree, int T_cap, int64_t B, c
                                 const rnad_step_params_t *device_params, void *scratch, const int32_t *lane_ids, const int32_t *items,
                                 const int32_t *n_items, double *norm, void *states, int32_t *alive, uint64_t *acts, float *final_reward,
                                 int32_t *visited, int visited_is_clear, void *stream) {
-    void *indices = states;
-    RNAD_REQUIRE(tree && table && scratch && lane_ids && items && n_items && indices && acts && final_reward, "rnad_bucket_play: null argument");
+    RNAD_REQUIRE(tree && table && scratch && lane_ids && items && n_items && states && acts && final_reward, "rnad_bucket_play: null argument");
     RNAD_REQUIRE(T_cap >= 1 && T_cap <= kCompactSteps && B >= 1, "rnad_bucket_play: 1 <= T_cap <= %d, got %d", kCompactSteps, T_cap);
     RNAD_REQUIRE(table_stride >= tree->A && (!rows == !n_rows), "rnad_bucket_play: bad table stride / row list");
-    const RolloutBuffers out{T_cap, B, indices, nullptr, nullptr, nullptr, nullptr, nullptr, alive, (unsigned long long *)acts, final_reward,
-                             visited};
-    return rollout_bucketed_impl(tree, out, true, table, table_stride, table_is_policy, nullptr, 1, seed, lane0, device_params, scratch,
-                                 const_cast<int32_t *>(lane_ids), const_cast<int32_t *>(items), const_cast<int32_t *>(n_items), norm,
-                                 (hipStream_t)stream, 2, nullptr, rows, n_rows, nullptr, nullptr, visited_is_clear != 0);
+    RolloutRequest rq{T_cap, B, {table, table_stride, table_is_policy}, {seed, lane0, device_params},
+                      {scratch, const_cast<int32_t *>(lane_ids), const_cast<int32_t *>(items), const_cast<int32_t *>(n_items), norm}, (hipStream_t)stream};
+    rq.phases = 2;
+    rq.out = {states, alive, (unsigned long long *)acts, final_reward, visited};
+    rq.play_rows = rows;
+    rq.n_play_rows = n_rows;
+    rq.visited_is_clear = visited_is_clear != 0;
+    return rollout_bucketed_impl(tree, read_switches(), rq);
 }
 
 extern "C" int rnad_bucket_alive(const rnad_tree_t *tree, int T_cap, int64_t B, const void *scratch, int32_t *alive, double *norm, void *stream) {
     RNAD_REQUIRE(tree && scratch && alive, "rnad_bucket_alive: null argument");
     RNAD_REQUIRE(T_cap >= 1 && T_cap <= kMaxSteps && B >= 1, "rnad_bucket_alive: bad shape");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_bucket_alive: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
-    RNAD_REQUIRE_SIZED(tree, B, p);
-    const Scratch s = carve_scratch(const_cast<void *>(scratch), B, p);
-    hipLaunchKernelGGL(k_bucket_alive, dim3(T_cap + 1), dim3(kThreads), 0, (hipStream_t)stream, (int)alive_rows(tree, B, p, true), T_cap + 1,
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_alive", true, p)) return rc;
+    const Scratch s = carve_scratch(const_cast<void *>(scratch), tree, B, p);
+    hipLaunchKernelGGL(k_bucket_alive, dim3(T_cap + 1), dim3(kThreads), 0, (hipStream_t)stream, (int)alive_rows(B, p, true), T_cap + 1,
                        (const int32_t *)s.alive_part, alive, norm);
     RNAD_HIP_OK(hipGetLastError());
     return 0;
@@ -3266,10 +3456,12 @@ extern "C" int rnad_rollout_bucketed(const rnad_tree_t *tree, const rnad_traj_t 
     RNAD_REQUIRE(tr->T_cap >= 1 && tr->T_cap <= kMaxSteps && tr->B >= 1, "rnad_rollout_bucketed: bad trajectory shape T_cap=%d B=%lld",
                  tr->T_cap, (long long)tr->B);
     RNAD_REQUIRE(table_stride >= tree->A && (!value_table || value_stride >= 1), "rnad_rollout_bucketed: bad table stride");
-    const RolloutBuffers out{(int)tr->T_cap, tr->B, tr->indices, tr->mask_bits, tr->policy, tr->actions, tr->rewards, tr->values, tr->alive,
-                             nullptr, nullptr, nullptr};
-    return rollout_bucketed_impl(tree, out, false, table, table_stride, table_is_policy, value_table, value_stride, seed, lane0, device_params,
-                                 scratch, lane_ids, items, n_items, norm, (hipStream_t)stream);
+    RolloutRequest rq{(int)tr->T_cap, tr->B, {table, table_stride, table_is_policy}, {seed, lane0, device_params},
+                      {scratch, lane_ids, items, n_items, norm}, (hipStream_t)stream};
+    rq.dense = tr;
+    rq.value_table = value_table;
+    rq.value_stride = value_stride;
+    return rollout_bucketed_impl(tree, read_switches(), rq);
 }
 
 extern "C" int rnad_rollout_bucketed_compact(const rnad_tree_t *tree, int T_cap, int64_t B, const float *table, int64_t table_stride,
@@ -3277,18 +3469,17 @@ extern "C" int rnad_rollout_bucketed_compact(const rnad_tree_t *tree, int T_cap,
                                              void *scratch, int32_t *lane_ids, int32_t *items, int32_t *n_items, double *norm,
                                              void *states, int32_t *alive, uint64_t *acts, float *final_reward, int32_t *visited,
                                              void *stream) {
-    void *indices = states;
-    RNAD_REQUIRE(tree && table && scratch && lane_ids && items && n_items && indices && acts && final_reward,
+    RNAD_REQUIRE(tree && table && scratch && lane_ids && items && n_items && states && acts && final_reward,
                  "rnad_rollout_bucketed_compact: null argument");
     RNAD_REQUIRE(alive || norm, "rnad_rollout_bucketed_compact: deferred alive counts (alive == NULL) need `norm` (it is cleared here)");
     RNAD_REQUIRE(T_cap >= 1 && T_cap <= kCompactSteps && B >= 1, "rnad_rollout_bucketed_compact: 1 <= T_cap <= %d (3 bits per step), got %d",
                  kCompactSteps, T_cap);
     RNAD_REQUIRE(table_stride >= tree->A, "rnad_rollout_bucketed_compact: bad table stride");
     static_assert(RNAD_MAX_ACTIONS <= 8, "3 bits per action");
-    const RolloutBuffers out{T_cap, B, indices, nullptr, nullptr, nullptr, nullptr, nullptr, alive, (unsigned long long *)acts, final_reward,
-                             visited};
-    return rollout_bucketed_impl(tree, out, true, table, table_stride, table_is_policy, nullptr, 1, seed, lane0, device_params, scratch,
-                                 lane_ids, items, n_items, norm, (hipStream_t)stream);
+    RolloutRequest rq{T_cap, B, {table, table_stride, table_is_policy}, {seed, lane0, device_params}, {scratch, lane_ids, items, n_items, norm},
+                      (hipStream_t)stream};
+    rq.out = {states, alive, (unsigned long long *)acts, final_reward, visited};
+    return rollout_bucketed_impl(tree, read_switches(), rq);
 }
 
 // rnad_rollout_bucketed_compact with the copies of rnad_rows_expand carried by its keys pass (distinct observations: the actor's table and
@@ -3300,29 +3491,17 @@ extern "C" int rnad_rollout_bucketed_compact_expand(const rnad_tree_t *tree, int
                                                     int32_t *n_items, double *norm, void *states, int32_t *alive, uint64_t *acts,
                                                     float *final_reward, int32_t *visited, const int32_t *rep_of, int n_tables,
                                                     float *const *tables, const int32_t *floats_per_row, void *stream) {
-    void *indices = states;
-    RNAD_REQUIRE(tree && table && scratch && lane_ids && items && n_items && indices && acts && final_reward && rep_of && tables && floats_per_row,
+    RNAD_REQUIRE(tree && table && scratch && lane_ids && items && n_items && states && acts && final_reward && rep_of && tables && floats_per_row,
                  "rnad_rollout_bucketed_compact_expand: null argument");
     RNAD_REQUIRE(alive || norm, "rnad_rollout_bucketed_compact_expand: deferred alive counts (alive == NULL) need `norm` (it is cleared here)");
     RNAD_REQUIRE(T_cap >= 1 && T_cap <= kCompactSteps && B >= 1, "rnad_rollout_bucketed_compact_expand: 1 <= T_cap <= %d, got %d", kCompactSteps, T_cap);
     RNAD_REQUIRE(table_stride >= tree->A && table_is_policy, "rnad_rollout_bucketed_compact_expand: the actor must be a table of policy rows");
     RNAD_REQUIRE(n_tables >= 1 && n_tables <= 4, "rnad_rollout_bucketed_compact_expand: 1..4 tables");
-    KeysExpand ex;
-    ex.rep_of = rep_of;
-    ex.rows = 2 * tree->S;
-    ex.n = n_tables;
-    for (int k = 0; k < n_tables; ++k) {
-        RNAD_REQUIRE(tables[k] && floats_per_row[k] > 0 && floats_per_row[k] % 4 == 0 && ((uintptr_t)tables[k] & 15) == 0,
-                     "rnad_rollout_bucketed_compact_expand: table %d must be 16-byte aligned with a row of a multiple of 4 floats", k);
-        ex.tab[k] = reinterpret_cast<float4 *>(tables[k]);
-        ex.quads[k] = floats_per_row[k] / 4;
-        ex.max_quads = std::max(ex.max_quads, ex.quads[k]);
-    }
-    const RolloutBuffers out{T_cap, B, indices, nullptr, nullptr, nullptr, nullptr, nullptr, alive, (unsigned long long *)acts, final_reward,
-                             visited};
-    return rollout_bucketed_impl(tree, out, true, table, table_stride, table_is_policy, nullptr, 1, seed, lane0, device_params, scratch,
-                                 lane_ids, items, n_items, norm, (hipStream_t)stream, 3, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr,
-                                 nullptr, &ex);
+    RolloutRequest rq{T_cap, B, {table, table_stride, table_is_policy}, {seed, lane0, device_params}, {scratch, lane_ids, items, n_items, norm},
+                      (hipStream_t)stream};
+    rq.out = {states, alive, (unsigned long long *)acts, final_reward, visited};
+    if (int rc = keys_expand_for("rnad_rollout_bucketed_compact_expand", tree, rep_of, n_tables, tables, floats_per_row, rq.expand)) return rc;
+    return rollout_bucketed_impl(tree, read_switches(), rq);
 }
 
 // rnad_rollout_bucketed_compact(_expand) and rnad_learn_bucketed_compact of the batch it plays, T = T_cap, in one call: keys, sort, then
@@ -3351,35 +3530,25 @@ extern "C" int rnad_rollout_learn_bucketed_compact(const rnad_tree_t *tree, int 
     RNAD_REQUIRE(!rows == !n_rows, "rnad_rollout_learn_bucketed_compact: rows and n_rows go together");
     RNAD_REQUIRE(n_tables >= 0 && n_tables <= 4 && (n_tables == 0 || (rep_of && tables && floats_per_row)),
                  "rnad_rollout_learn_bucketed_compact: 0..4 tables to expand, with rep_of");
-    KeysExpand ex;
-    if (n_tables > 0) {
-        ex.rep_of = rep_of;
-        ex.rows = 2 * tree->S;
-        ex.n = n_tables;
-        for (int k = 0; k < n_tables; ++k) {
-            RNAD_REQUIRE(tables[k] && floats_per_row[k] > 0 && floats_per_row[k] % 4 == 0 && ((uintptr_t)tables[k] & 15) == 0,
-                         "rnad_rollout_learn_bucketed_compact: table %d must be 16-byte aligned with a row of a multiple of 4 floats", k);
-            ex.tab[k] = reinterpret_cast<float4 *>(tables[k]);
-            ex.quads[k] = floats_per_row[k] / 4;
-            ex.max_quads = std::max(ex.max_quads, ex.quads[k]);
-        }
-    }
+    const Switches sw = read_switches();
     const FusedLearn fused{fast_records, hp, accumulators, (flags & RNAD_PLAY_LEARN_DISTINCT) != 0, leaf};
-    const RolloutBuffers out{T_cap, B, states, nullptr, nullptr, nullptr, nullptr, nullptr, alive, (unsigned long long *)acts, final_reward, nullptr};
-    if (int rc = rollout_bucketed_impl(tree, out, true, table, table_stride, 1, nullptr, 1, seed, lane0, device_params, scratch, lane_ids, items,
-                                       n_items, norm, (hipStream_t)stream, 3, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr,
-                                       n_tables > 0 ? &ex : nullptr, &fused))
-        return rc;
+    RolloutRequest rq{T_cap, B, {table, table_stride, 1}, {seed, lane0, device_params}, {scratch, lane_ids, items, n_items, norm}, (hipStream_t)stream};
+    rq.out = {states, alive, (unsigned long long *)acts, final_reward};
+    rq.fused = &fused;
+    if (n_tables > 0)
+        if (int rc = keys_expand_for("rnad_rollout_learn_bucketed_compact", tree, rep_of, n_tables, tables, floats_per_row, rq.expand)) return rc;
+    if (int rc = rollout_bucketed_impl(tree, sw, rq)) return rc;
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_rollout_learn_bucketed_compact: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
-    const CountReps cr = count_reps(tree, p, accumulators, T_cap + 1, alive, norm);
+    if (int rc = plan_for(tree, B, sw, "rnad_rollout_learn_bucketed_compact", false, p)) return rc;
+    const Accumulators acc = carve_accumulators(accumulators, tree, p);
     if (!finish) {  // the counts on their own: the caller all-reduces `norm` before its rnad_bucket_finish
-        hipLaunchKernelGGL(k_bucket_alive_rep, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, cr.T1, cr.alive_rep, cr.norm_rep, alive, norm);
+        hipLaunchKernelGGL(k_bucket_alive_rep, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, T_cap + 1, acc.alive_rep, acc.norm_rep, alive, norm);
         RNAD_HIP_OK(hipGetLastError());
         return 0;
     }
     RNAD_REQUIRE(norm_global != norm, "rnad_rollout_learn_bucketed_compact: norm_global must not be the `norm` output");
-    return finish_impl(tree, p, norm_global, hp, accumulators, nullptr, dlogit_tab, dv_tab, rows, n_rows, groups, (hipStream_t)stream, &cr);
+    const Counts counts{T_cap + 1, alive, norm};
+    return finish_impl(tree, p, acc, norm_global, hp, {nullptr, dlogit_tab, dv_tab, rows, n_rows, groups}, (hipStream_t)stream, &counts);
 }
 
 // The dense buffers of a compact trajectory: slot (t, j) from indices[t, j] (and indices[t + 1, j] for the reward) alone.
@@ -3440,92 +3609,74 @@ extern "C" int rnad_bucket_expand(const rnad_tree_t *tree, int T, int64_t B, con
 }
 
 namespace {
-// upper rows out of their replicas, then sums -> normalised fp32 tables (and the two logged losses)
-int finish_impl(const rnad_tree_t *tree, const Plan &p, const double *norm, const rnad_learn_params_t *hp, void *accumulators, double *losses,
-                float *dlogit_tab, float *dv_tab, const int32_t *rows, const int64_t *n_rows, const rnad_row_groups_t *groups,
-                hipStream_t stream, const CountReps *counts) {
-    const int64_t S = tree->S, A1 = tree->A + 1;
-    unsigned long long *acc = (unsigned long long *)accumulators;
-    unsigned long long *rep = acc + 2 * S * A1;
-    const int nu = p.cut->n_upper;
-    double *losses_raw = (double *)(rep + (int64_t)kReplicas * 2 * std::max(nu, 1) * A1);
-    int32_t *overflow = (int32_t *)(losses_raw + 4);
-    const FixedPoint fx = fixed_point_for(*hp);
-    const int n_multi = groups ? groups->n_groups : 0;
-    RNAD_REQUIRE(n_multi >= 0 && (n_multi == 0 || (groups->start && groups->order && rows)),
-                 "rnad_bucket_finish: row groups come with their start / order arrays and with the list of the rows outside them");
-    ProfScope fin(PROF_BUCKET_FINISH, stream);
-    const unsigned row_blocks = std::min(blocks_for(2 * S, kThreads * kFinishRows), 512u), upper_blocks = nu > 0 ? blocks_for(2 * (int64_t)nu, kThreads / 64) : 0;
-    const unsigned group_blocks = n_multi > 0 ? blocks_for(n_multi, kThreads / 64) : 0;
-    RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_bucket_finish<kA>), dim3(row_blocks + upper_blocks + group_blocks), dim3(kThreads), 0, stream, S,
-                                                (int)row_blocks, rows, n_rows, nu, p.cut->n_groups, (const int32_t *)p.cut->upper_list,
-                                                (const int32_t *)p.cut->bucket_of, acc, rep, norm, hp->w_v, hp->w_n, fx, overflow,
-                                                losses_raw, losses, dlogit_tab, dv_tab, (int)upper_blocks, n_multi,
-                                                n_multi ? groups->start : (const int32_t *)nullptr,
-                                                n_multi ? groups->order : (const int32_t *)nullptr,
-                                                n_multi ? groups->first : (const int32_t *)nullptr, (groups && rows) ? groups->rows_below_cut : 0, counts ? counts->alive_rep : (int32_t *)nullptr,
-                                                counts ? counts->norm_rep : (double *)nullptr, counts ? counts->T1 : 0,
-                                                counts ? counts->alive_out : (int32_t *)nullptr, counts ? counts->norm_out : (double *)nullptr));
-    RNAD_HIP_OK(hipGetLastError());
-    return 0;
+struct LearnRequest {  // what an entry point asks of learn_bucketed_impl: the dense trajectory or -- acts set -- the compact one
+    int T;
+    int64_t B;
+    const void *indices;  // dense: int32 state ids [T, B]; compact: the relative states
+    const float *records;
+    const int32_t *items, *n_items;
+    const double *norm;  // NULL: the caller completes the update with rnad_bucket_finish once the normalisers are known
+    const rnad_learn_params_t *hp;
+    void *accumulators;
+    FinishOut out;
+    hipStream_t stream;
+    const int32_t *actions = nullptr;  // dense
+    const float *rewards = nullptr, *mu = nullptr;
+    const unsigned long long *acts = nullptr;  // compact
+    const float *final_reward = nullptr, *fast = nullptr;
+    const void *rollout_scratch = nullptr;  // compact, optional: the rollout left its alive counts there; they are added up here, into ...
+    int rollout_T_cap = 0;
+    int32_t *alive_out = nullptr;  // ...
+    double *norm_out = nullptr;
+};
+
+template <int A, class REL, bool LOSSES>
+int launch_learn_c(const rnad_tree_t *tree, const Plan &p, const LearnRequest &rq, const Accumulators &acc, const FixedPoint &fx) {
+    const BucketCut &cut = *p.cut;
+    const int T1 = rq.rollout_T_cap + 1;
+    const int32_t *alive_part = rq.rollout_scratch ? carve_scratch(const_cast<void *>(rq.rollout_scratch), tree, rq.B, p).alive_part : nullptr;
+    const unsigned grid = (unsigned)std::max<int64_t>(p.max_items, alive_part ? T1 : 0);
+    return launch_lds(k_bucket_learn_c<A, REL, LOSSES>, dim3(grid), dim3(kThreads), (size_t)p.lds, rq.stream, rq.T, rq.B, tree->S, cut.rows, p.path_words,
+                      cut.n_groups, std::max(cut.n_upper, 1), (const Item *)rq.items, rq.n_items, (const int32_t *)cut.bucket_of,
+                      (const int32_t *)cut.bucket_lo, (const int32_t *)cut.bucket_path, (const int32_t *)cut.path_states,
+                      std::max(cut.max_path, 1), (const REL *)rq.indices, rq.fast, rq.acts, rq.final_reward, rq.records, *rq.hp, fx, acc.acc, acc.rep,
+                      rq.out.losses ? acc.losses_raw : (double *)nullptr, acc.overflow, alive_part, (int)alive_rows(rq.B, p, true), T1,
+                      rq.alive_out, rq.norm_out, (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, LeafCount{});
 }
 
-int learn_bucketed_impl(const rnad_tree_t *tree, int T, int64_t B, const void *indices, const int32_t *actions, const float *rewards,
-                        const float *mu, const unsigned long long *acts, const float *final_reward, const float *records,
-                        const float *fast, const int32_t *items, const int32_t *n_items, const double *norm, const rnad_learn_params_t *hp,
-                        void *accumulators, double *losses, float *dlogit_tab, float *dv_tab, const int32_t *rows, const int64_t *n_rows,
-                        const void *rollout_scratch, int rollout_T_cap, int32_t *alive_out, double *norm_out, const rnad_row_groups_t *groups,
-                        hipStream_t stream) {
-    const bool compact = acts != nullptr;  // (indices: the relative states then)
+template <int A>
+int launch_learn_dense(const rnad_tree_t *tree, const Plan &p, const LearnRequest &rq, const Accumulators &acc, const FixedPoint &fx) {
+    const BucketCut &cut = *p.cut;
+    return launch_lds(k_bucket_learn<A>, dim3((unsigned)p.max_items), dim3(kThreads), (size_t)p.lds, rq.stream, rq.T, rq.B, tree->S, cut.rows,
+                      p.path_words, cut.n_groups, std::max(cut.n_upper, 1), (const Item *)rq.items, rq.n_items, (const int32_t *)cut.bucket_of,
+                      (const int32_t *)cut.bucket_lo, (const int32_t *)cut.bucket_path, (const int32_t *)rq.indices, rq.actions, rq.rewards, rq.mu,
+                      rq.records, *rq.hp, fx, acc.acc, acc.rep, rq.out.losses ? acc.losses_raw : (double *)nullptr, acc.overflow);
+}
+
+int learn_bucketed_impl(const rnad_tree_t *tree, const Switches &sw, const LearnRequest &rq) {
+    const bool compact = rq.acts != nullptr;
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_learn_bucketed: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
-    const int64_t S = tree->S, A1 = tree->A + 1;
-    unsigned long long *acc = (unsigned long long *)accumulators;
-    unsigned long long *rep = acc + 2 * S * A1;
-    const int nu = p.cut->n_upper;
-    double *losses_raw = (double *)(rep + (int64_t)kReplicas * 2 * std::max(nu, 1) * A1);
-    int32_t *overflow = (int32_t *)(losses_raw + 4);
-    const FixedPoint fx = fixed_point_for(*hp);
-    const int32_t *alive_part = nullptr;
-    const int T1 = rollout_T_cap + 1;
-    if (rollout_scratch) alive_part = carve_scratch(const_cast<void *>(rollout_scratch), B, p).alive_part;
-    const unsigned learn_grid = (unsigned)std::max<int64_t>(p.max_items, alive_part ? T1 : 0);
+    if (int rc = plan_for(tree, rq.B, sw, "rnad_learn_bucketed", false, p)) return rc;
+    const Accumulators acc = carve_accumulators(rq.accumulators, tree, p);
+    const FixedPoint fx = fixed_point_for(*rq.hp);
     // (the loss sums and the overflow flag are zero here: k_bucket_finish of the previous update cleared them.  Not hipMemsetAsync:
     // the memset node of a captured graph was seen to write garbage after ~57 replays on ROCm 7.2,
     // tests/test_hip_graph.py::test_many_replays_stay_finite)
-    ProfScope prof(PROF_LEARN, stream);
-#define RNAD_BUCKET_LEARN_C(LOSSES)                                                                                                   \
-    do {                                                                                                                              \
-        auto kern = k_bucket_learn_c<kA, REL, LOSSES>;                                                                                \
-        if (p.lds > 48 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds)); \
-        hipLaunchKernelGGL(kern, dim3(learn_grid), dim3(kThreads), (size_t)p.lds, stream, T, B, S, p.cut->rows, p.path_words,         \
-                           p.cut->n_groups, std::max(nu, 1), (const Item *)items, n_items, (const int32_t *)p.cut->bucket_of,         \
-                           (const int32_t *)p.cut->bucket_lo, (const int32_t *)p.cut->bucket_path, (const int32_t *)p.cut->path_states, \
-                           std::max(p.cut->max_path, 1), (const REL *)indices, fast, acts, final_reward, records, *hp, fx, acc, rep,  \
-                           losses ? losses_raw : (double *)nullptr, overflow, alive_part, (int)alive_rows(tree, B, p, true), T1,      \
-                           alive_out, norm_out, (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, LeafCount{}); \
-    } while (0)
+    ProfScope prof(PROF_LEARN, rq.stream);
     {
-        ProfScope one(PROF_BUCKET_LEARN, stream);
-        if (compact && (losses || fx.check_l)) {  // (the LOSSES instantiation also range-checks the dL/dlogit addends of a clip >= 2^29)
-            RNAD_REQUIRE(records, "rnad_learn_bucketed_compact: a NeuRD clip of 2^29 or more needs the dense records too");
-            RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, RNAD_BUCKET_LEARN_C(true)));
+        ProfScope one(PROF_BUCKET_LEARN, rq.stream);
+        if (compact && (rq.out.losses || fx.check_l)) {  // (the LOSSES instantiation also range-checks the dL/dlogit addends of a clip >= 2^29)
+            RNAD_REQUIRE(rq.records, "rnad_learn_bucketed_compact: a NeuRD clip of 2^29 or more needs the dense records too");
+            RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, if (int rc = launch_learn_c<kA, REL, true>(tree, p, rq, acc, fx)) return rc));
         } else if (compact) {
-            RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, RNAD_BUCKET_LEARN_C(false)));
+            RNAD_DISPATCH_REL(p, RNAD_DISPATCH_A(tree->A, if (int rc = launch_learn_c<kA, REL, false>(tree, p, rq, acc, fx)) return rc));
         } else {
-            if (p.lds > 48 * 1024)
-                RNAD_DISPATCH_A(tree->A, RNAD_HIP_OK(hipFuncSetAttribute((const void *)k_bucket_learn<kA>, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds)));
-            RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_bucket_learn<kA>), dim3((unsigned)p.max_items), dim3(kThreads), (size_t)p.lds, stream, T, B, S,
-                                                        p.cut->rows, p.path_words, p.cut->n_groups, std::max(nu, 1), (const Item *)items, n_items,
-                                                        (const int32_t *)p.cut->bucket_of, (const int32_t *)p.cut->bucket_lo,
-                                                        (const int32_t *)p.cut->bucket_path, (const int32_t *)indices, actions, rewards, mu, records,
-                                                        *hp, fx, acc, rep, losses ? losses_raw : (double *)nullptr, overflow));
+            RNAD_DISPATCH_A(tree->A, if (int rc = launch_learn_dense<kA>(tree, p, rq, acc, fx)) return rc);
         }
     }
-#undef RNAD_BUCKET_LEARN_C
     RNAD_HIP_OK(hipGetLastError());
-    if (!norm) return 0;  // the caller completes the update with rnad_bucket_finish once the normalisers are known
-    return finish_impl(tree, p, norm, hp, accumulators, losses, dlogit_tab, dv_tab, rows, n_rows, groups, stream);
+    if (!rq.norm) return 0;
+    return finish_impl(tree, p, acc, rq.norm, rq.hp, rq.out, rq.stream);
 }
 }  // namespace
 
@@ -3534,7 +3685,7 @@ extern "C" int rnad_bucket_indices(const rnad_tree_t *tree, int T1, int64_t B, c
     RNAD_REQUIRE(tree && states && items && n_items && indices, "rnad_bucket_indices: null argument");
     RNAD_REQUIRE(T1 >= 1 && T1 <= kCompactSteps + 1 && B >= 1, "rnad_bucket_indices: bad shape");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_bucket_indices: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_indices", false, p)) return rc;
     RNAD_DISPATCH_REL(p, hipLaunchKernelGGL((k_bucket_indices<REL>), dim3((unsigned)p.max_items), dim3(kThreads), 0, (hipStream_t)stream, T1, B,
                                             (const Item *)items, n_items, (const int32_t *)p.cut->bucket_path, (const int32_t *)p.cut->bucket_lo,
                                             (const int32_t *)p.cut->path_states, std::max(p.cut->max_path, 1), p.cut->n_groups, (const REL *)states,
@@ -3548,7 +3699,7 @@ extern "C" int rnad_bucket_pack_states(const rnad_tree_t *tree, int T1, int64_t 
     RNAD_REQUIRE(tree && states && items && n_items && indices && mismatch, "rnad_bucket_pack_states: null argument");
     RNAD_REQUIRE(T1 >= 1 && T1 <= kCompactSteps + 1 && B >= 1, "rnad_bucket_pack_states: bad shape");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_bucket_pack_states: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_pack_states", false, p)) return rc;
     RNAD_DISPATCH_REL(p, hipLaunchKernelGGL((k_bucket_pack<REL>), dim3((unsigned)p.max_items), dim3(kThreads), 0, (hipStream_t)stream, T1, B, p.cut->rows,
                                             (const Item *)items, n_items, (const int32_t *)p.cut->bucket_path, (const int32_t *)p.cut->bucket_lo,
                                             (const int32_t *)p.cut->path_states, std::max(p.cut->max_path, 1), p.cut->n_groups, indices,
@@ -3563,7 +3714,7 @@ extern "C" int rnad_leaf_paths_pack(const rnad_tree_t *tree, int64_t plan_B, int
     RNAD_REQUIRE(tree && states && items && n_items && indices && mismatch && rows_out && rel_bytes_out, "rnad_leaf_paths_pack: null argument");
     RNAD_REQUIRE(T1 >= 1 && T1 <= kCompactSteps + 1 && n_cols >= 1 && max_items >= 1, "rnad_leaf_paths_pack: bad shape");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, plan_B, p), "rnad_leaf_paths_pack: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
+    if (int rc = plan_for(tree, plan_B, read_switches(), "rnad_leaf_paths_pack", false, p)) return rc;
     // (a lane's bucket and its leaf column's bucket pair up because every episode leaves the tree inside the window: T1 - 1 = 2 * depth steps
     // are enough on any tree, ragged episode lengths included -- tests/test_hip_leaf.py plays those)
     RNAD_REQUIRE(T1 - 1 == 2 * tree->max_depth, "rnad_leaf_paths_pack: leaf paths span the whole window, T1 = 2 * depth + 1");
@@ -3583,8 +3734,9 @@ extern "C" int rnad_bucket_finish(const rnad_tree_t *tree, int64_t B, const doub
     RNAD_REQUIRE(tree && norm && hp && accumulators && dlogit_tab && dv_tab, "rnad_bucket_finish: null argument");
     RNAD_REQUIRE(!rows == !n_rows, "rnad_bucket_finish: rows and n_rows go together");
     Plan p;
-    RNAD_REQUIRE(make_plan(tree, B, p), "rnad_bucket_finish: this tree / batch cannot be bucketed (see rnad_bucket_plan)");
-    return finish_impl(tree, p, norm, hp, accumulators, losses, dlogit_tab, dv_tab, rows, n_rows, groups, (hipStream_t)stream);
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_finish", false, p)) return rc;
+    return finish_impl(tree, p, carve_accumulators(accumulators, tree, p), norm, hp, {losses, dlogit_tab, dv_tab, rows, n_rows, groups},
+                       (hipStream_t)stream);
 }
 
 extern "C" int rnad_learn_bucketed(const rnad_tree_t *tree, int T, int64_t B, const int32_t *indices, const int32_t *actions,
@@ -3594,9 +3746,11 @@ extern "C" int rnad_learn_bucketed(const rnad_tree_t *tree, int T, int64_t B, co
     RNAD_REQUIRE(tree && indices && actions && rewards && mu && records && items && n_items && hp && accumulators && dlogit_tab && dv_tab,
                  "rnad_learn_bucketed: null argument");
     RNAD_REQUIRE(T >= 1 && B >= 1, "rnad_learn_bucketed: bad shape");
-    return learn_bucketed_impl(tree, T, B, indices, actions, rewards, mu, nullptr, nullptr, records, nullptr, items, n_items, norm, hp,
-                               accumulators, losses, dlogit_tab, dv_tab, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                               (hipStream_t)stream);
+    LearnRequest rq{T, B, indices, records, items, n_items, norm, hp, accumulators, {losses, dlogit_tab, dv_tab}, (hipStream_t)stream};
+    rq.actions = actions;
+    rq.rewards = rewards;
+    rq.mu = mu;
+    return learn_bucketed_impl(tree, read_switches(), rq);
 }
 
 extern "C" int rnad_learn_bucketed_compact(const rnad_tree_t *tree, int T, int64_t B, const void *states, const uint64_t *acts,
@@ -3608,13 +3762,19 @@ extern "C" int rnad_learn_bucketed_compact(const rnad_tree_t *tree, int T, int64
     RNAD_REQUIRE(!rows == !n_rows, "rnad_learn_bucketed_compact: rows and n_rows go together");
     RNAD_REQUIRE(!rollout_scratch || (alive && rollout_T_cap >= T && rollout_T_cap <= kCompactSteps),
                  "rnad_learn_bucketed_compact: completing the rollout's alive counts needs `alive` and the rollout's T_cap");
-    const void *indices = states;
-    RNAD_REQUIRE(tree && indices && acts && final_reward && fast_records && items && n_items && hp && accumulators && dlogit_tab && dv_tab,
+    RNAD_REQUIRE(tree && states && acts && final_reward && fast_records && items && n_items && hp && accumulators && dlogit_tab && dv_tab,
                  "rnad_learn_bucketed_compact: null argument");
     RNAD_REQUIRE(!losses || records, "rnad_learn_bucketed_compact: the losses need the dense records (logits)");
     RNAD_REQUIRE(((uintptr_t)fast_records & 15) == 0, "rnad_learn_bucketed_compact: fast_records must be 16-byte aligned");
     RNAD_REQUIRE(T >= 1 && T <= kCompactSteps && B >= 1, "rnad_learn_bucketed_compact: bad shape");
-    return learn_bucketed_impl(tree, T, B, indices, nullptr, nullptr, nullptr, (const unsigned long long *)acts, final_reward, records,
-                               fast_records, items, n_items, norm, hp, accumulators, losses, dlogit_tab, dv_tab, rows, n_rows,
-                               rollout_scratch, rollout_T_cap, alive, norm_out, groups, (hipStream_t)stream);
+    LearnRequest rq{T, B, states, records, items, n_items, norm, hp, accumulators, {losses, dlogit_tab, dv_tab, rows, n_rows, groups},
+                    (hipStream_t)stream};
+    rq.acts = (const unsigned long long *)acts;
+    rq.final_reward = final_reward;
+    rq.fast = fast_records;
+    rq.rollout_scratch = rollout_scratch;
+    rq.rollout_T_cap = rollout_T_cap;
+    rq.alive_out = alive;
+    rq.norm_out = norm_out;
+    return learn_bucketed_impl(tree, read_switches(), rq);
 }
