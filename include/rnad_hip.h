@@ -556,6 +556,21 @@ int rnad_bucket_pack_states(const rnad_tree_t *tree, int T1, int64_t B, const in
 int rnad_bucket_expand(const rnad_tree_t *tree, int T, int64_t B, const int32_t *indices, const uint64_t *acts,
                        const float *final_reward, const float *records, uint8_t *mask_bits, float *policy, int32_t *actions,
                        float *rewards, void *stream);
+/* The logged statistics of rnad.py:427-452 from the first T steps of a compact trajectory, without its dense buffers.  Every logged
+ * quantity is a per-row quantity weighted with the number of live slots of the batch in that (player, state) row r = p * S + s:
+ *   1. per row, fp32, once: row_stats[r] = {e, e', k, sum, lo, hi, 0, 0} with pi = the pi columns of records[r], pi' = policy head of
+ *      logit_target_tab[r] (f32 [2S, A]) under the row's legal bits, q = 1 / (float)popcount(legal):
+ *        e = sum_legal pi (logf(pi) - logf(q)), e' the same with pi', k = sum_legal pi (logf(pi) - logf(pi))   (util/metric.kld per element;
+ *        no special case for pi = 0: the reference's NaN comes out as NaN), sum / lo / hi = sum, min, max of the row's A learner logits;
+ *   2. one workgroup per work item counts the item's slots per row c_r (slot (t, j) is in the state rnad_bucket_indices rebuilds; t & 1
+ *      moves) and adds count x statistic up in fp64;
+ *   3. the absorbed slots of parity p, z_p = sum_{t < T, t & 1 = p} (B - alive[t]), gather row p * S + 0 in the reference's logit statistics.
+ * out (device f64 [8], initialised by the call) = {sum c e, sum c e', sum c k, N = sum c, sum of the logits of all T * B slots,
+ * min, max of the logits over the rows with c_r > 0 (and row p * S where z_p > 0), 0}.  Only the order of the per-workgroup fp64 additions
+ * varies from run to run.  row_stats: f32 [2S][8], caller-owned scratch.  alive: the rollout's int32 [>= T] counts, complete.  T <= 21. */
+int rnad_bucket_log_stats(const rnad_tree_t *tree, int T, int64_t B, const void *states, const int32_t *items, const int32_t *n_items,
+                          const int32_t *alive, const float *records, const float *logit_target_tab, float *row_stats, double *out,
+                          void *stream);
 int64_t rnad_bucket_record_stride(int A);
 int64_t rnad_bucket_fast_record_stride(int A);
 int64_t rnad_bucket_policy_row_stride(int A);

@@ -1828,6 +1828,187 @@ __global__ __launch_bounds__(kThreads) void k_bucket_pack(int T1, int64_t B, int
     }
 }
 
+// ---------------------------------------------------------------------------------------- logged statistics (rnad.py:427-452)
+// Every logged scalar is a per-row quantity weighted with the number of live slots of the batch in that (player, state) row, so: the
+// statistics once per row (k_log_row_stats, 2S threads), the visits per row counted from the compact trajectory by the learner's work
+// items (k_log_count: LDS counters indexed like the learner's table, the path steps once per workgroup), the absorbed slots' share of the
+// logit statistics from alive[] (k_log_finish).  Products count x fp32 and all sums in fp64; min / max travel as order-preserving
+// 64-bit integers (atomicMin / atomicMax) and k_log_finish turns them back into doubles.
+constexpr int kLogStat = 8;  // floats of a row's statistics: e | e' | k | sum | lo | hi | 0 | 0  (32 bytes)
+enum { LOG_E = 0, LOG_ET = 1, LOG_K = 2, LOG_N = 3, LOG_SUM = 4, LOG_MIN = 5, LOG_MAX = 6, LOG_SPARE = 7 };
+
+__device__ __forceinline__ unsigned long long ordered_of(double d) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double double_of_ordered(unsigned long long e) {
+    return __longlong_as_double((long long)((e >> 63) ? (e & 0x7fffffffffffffffull) : ~e));
+}
+
+template <int A>
+__global__ __launch_bounds__(kThreads) void k_log_row_stats(int64_t rows, const float *__restrict__ rec_, const float *__restrict__ logit_target,
+                                                            float *__restrict__ row_stats, double *__restrict__ out) {
+    if (blockIdx.x == 0 && threadIdx.x < kLogStat) {  // (the counting launch that adds into `out` follows on the stream)
+        double init = 0.0;
+        if (threadIdx.x == LOG_MIN) init = __longlong_as_double((long long)ordered_of(__longlong_as_double(0x7ff0000000000000ll)));   // +inf
+        if (threadIdx.x == LOG_MAX) init = __longlong_as_double((long long)ordered_of(__longlong_as_double((long long)0xfff0000000000000ull)));  // -inf
+        out[threadIdx.x] = init;
+    }
+    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= rows) return;
+    constexpr int RS = kRowStride<A>;
+    float rec[RS];
+    const float4 *rp = reinterpret_cast<const float4 *>(rec_ + r * RS);
+#pragma unroll
+    for (int u = 0; u < RS / 4; ++u) {
+        const float4 r4 = rp[u];
+        rec[4 * u] = r4.x; rec[4 * u + 1] = r4.y; rec[4 * u + 2] = r4.z; rec[4 * u + 3] = r4.w;
+    }
+    const uint32_t bits = __float_as_uint(rec[3 * A + 2]) & ((1u << A) - 1u);
+    float lt[A], pit[A], lpt[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) lt[a] = logit_target[r * A + a];
+    policy_head<A>(lt, bits, pit, lpt);
+    // util/metric.kld per element: p * (log p - log q), q = normalize(masks, p=1) = 1 / n on a legal action; no special case for p = 0
+    const float log_q = logf(1.0f / (float)__popc(bits));
+    float e = 0.0f, et = 0.0f, k = 0.0f, sum = 0.0f, lo = rec[0], hi = rec[0];
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        const float lg = rec[a], pi = rec[3 * A + 3 + a];
+        sum += lg;
+        lo = fminf(lo, lg);
+        hi = fmaxf(hi, lg);
+        if ((bits >> a) & 1) {
+            const float log_pi = logf(pi);
+            e += pi * (log_pi - log_q);
+            et += pit[a] * (logf(pit[a]) - log_q);
+            k += pi * (log_pi - log_pi);  // the acting policy of the on-policy batch is the record's own pi: 0, or the reference's NaN
+        }
+    }
+    float4 *o4 = reinterpret_cast<float4 *>(row_stats + r * kLogStat);
+    o4[0] = float4{e, et, k, sum};
+    o4[1] = float4{lo, hi, 0.0f, 0.0f};
+}
+
+struct LogAcc {
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // LOG_E .. LOG_SUM
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    __device__ __forceinline__ void add_row(const float *__restrict__ row_stats, uint32_t row, int count) {
+        const float4 *sp = at_bytes<float4>(row_stats, row * (uint32_t)(kLogStat * sizeof(float)));
+        const float4 a = sp[0], b = sp[1];
+        const double c = (double)count;  // (a 32-bit count times a 24-bit significand: exact)
+        s[LOG_E] += c * (double)a.x;
+        s[LOG_ET] += c * (double)a.y;
+        s[LOG_K] += c * (double)a.z;
+        s[LOG_N] += c;
+        s[LOG_SUM] += c * (double)a.w;
+        lo = fminf(lo, b.x);
+        hi = fmaxf(hi, b.y);
+    }
+};
+
+// One workgroup per work item, the items and the thread <-> lane map of k_bucket_learn_c / k_bucket_indices.  Steps the whole item shares
+// (t < n_shared: path_states) are counted once per workgroup with the item's lane count; below, a slot's relative state indexes an LDS
+// counter (state - bucket_lo, both players) and the workgroup multiplies its non-zero counters with the rows' statistics at the end.  A slot
+// that has no counter (tab_rows == 0: the table does not fit; a terminal bucket) gathers its row's statistics itself.
+template <typename REL>
+__global__ __launch_bounds__(kThreads) void k_log_count(int T, int64_t B, int64_t S, int tab_rows, int n_groups, const Item *__restrict__ items,
+                                                        const int32_t *__restrict__ n_items, const int32_t *__restrict__ bucket_lo,
+                                                        const int32_t *__restrict__ bucket_path, const int32_t *__restrict__ path_states,
+                                                        int path_stride, const REL *__restrict__ states, const float *__restrict__ row_stats,
+                                                        double *__restrict__ out) {
+    extern __shared__ int32_t visits[];  // [2][tab_rows]
+    __shared__ double part[kThreads / 64][5];
+    __shared__ float part_lo[kThreads / 64], part_hi[kThreads / 64];
+    if ((int)blockIdx.x >= *n_items) return;
+    const Item item = items[blockIdx.x];
+    const int path_word = bucket_path[item.bucket];
+    const int n_shared = (path_word & (kSharedRoot - 1)) + ((item.bucket < n_groups && (path_word & kSharedRoot)) ? 2 : 0);
+    const int lo = bucket_lo[item.bucket];
+    const int32_t *my_path = path_states + (int64_t)item.bucket * path_stride;
+    const int n_tab = item.bucket < n_groups ? tab_rows : 0;
+    const uint32_t B32 = (uint32_t)B, S32 = (uint32_t)S;
+    for (int i = threadIdx.x; i < 2 * n_tab; i += kThreads) visits[i] = 0;
+    __syncthreads();
+    LogAcc acc;
+    const int t_low = min(T, n_shared);
+    for (int k = threadIdx.x; k < item.count; k += kThreads) {
+        const uint32_t j = (uint32_t)(item.begin + k);
+        for (int t = t_low; t < T; ++t) {
+            const int rel = (int)*at_bytes<REL>(states, ((uint32_t)t * B32 + j) * (uint32_t)sizeof(REL));
+            if (rel == 0) continue;  // absorbed (rnad.py:369)
+            if (rel <= n_tab) {
+                atomicAdd(&visits[(t & 1) * n_tab + rel - 1], 1);
+            } else {
+                const uint32_t state = (uint32_t)(lo + rel - 1);
+                if (state < S32) acc.add_row(row_stats, (uint32_t)(t & 1) * S32 + state, 1);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * n_tab; i += kThreads) {
+        const int count = visits[i];
+        if (count == 0) continue;
+        const int p = i >= n_tab ? 1 : 0;
+        const uint32_t state = (uint32_t)(lo + i - p * n_tab);
+        if (state < S32) acc.add_row(row_stats, (uint32_t)p * S32 + state, count);
+    }
+    if ((int)threadIdx.x < t_low) {  // the item's own path: every lane of it sits in that state
+        const uint32_t state = (uint32_t)my_path[threadIdx.x];
+        if (state != 0 && state < S32) acc.add_row(row_stats, (threadIdx.x & 1u) * S32 + state, item.count);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) acc.s[q] += __shfl_down(acc.s[q], off, 64);
+        acc.lo = fminf(acc.lo, __shfl_down(acc.lo, off, 64));
+        acc.hi = fmaxf(acc.hi, __shfl_down(acc.hi, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) part[threadIdx.x >> 6][q] = acc.s[q];
+        part_lo[threadIdx.x >> 6] = acc.lo;
+        part_hi[threadIdx.x >> 6] = acc.hi;
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        double x = 0.0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) x += part[w][threadIdx.x];
+        if (x != 0.0) atomicAdd(out + threadIdx.x, x);  // (a NaN is != 0: it is added)
+    } else if (threadIdx.x == LOG_MIN || threadIdx.x == LOG_MAX) {
+        float m = threadIdx.x == LOG_MIN ? part_lo[0] : part_hi[0];
+#pragma unroll
+        for (int w = 1; w < kThreads / 64; ++w) m = threadIdx.x == LOG_MIN ? fminf(m, part_lo[w]) : fmaxf(m, part_hi[w]);
+        unsigned long long *dst = reinterpret_cast<unsigned long long *>(out + threadIdx.x);
+        if (threadIdx.x == LOG_MIN)
+            atomicMin(dst, ordered_of((double)m));
+        else
+            atomicMax(dst, ordered_of((double)m));
+    }
+}
+
+// The absorbed slots (state 0: the reference's logit statistics count the row of state 0 there) and the decoding of min / max.
+__global__ void k_log_finish(int T, int64_t B, int64_t S, const int32_t *__restrict__ alive, const float *__restrict__ row_stats,
+                             double *__restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double lo = double_of_ordered(reinterpret_cast<const unsigned long long *>(out)[LOG_MIN]);
+    double hi = double_of_ordered(reinterpret_cast<const unsigned long long *>(out)[LOG_MAX]);
+    double sum = out[LOG_SUM];
+    for (int p = 0; p < 2; ++p) {
+        int64_t z = 0;
+        for (int t = p; t < T; t += 2) z += B - (int64_t)alive[t];
+        if (z <= 0) continue;
+        const float *st = row_stats + (int64_t)p * S * kLogStat;
+        sum += (double)z * (double)st[3];
+        lo = fmin(lo, (double)st[4]);
+        hi = fmax(hi, (double)st[5]);
+    }
+    out[LOG_SUM] = sum;
+    out[LOG_MIN] = lo;
+    out[LOG_MAX] = hi;
+}
+
 // alive[t] = sum over the blocks of alive_part[block][t]; norm[P] += alive[t] for the steps of parity P: the loss normalisers N_P
 // of learn/vtrace.py:373,388 (f64 sums of integers: exact in any order; zeroed by k_bucket_keys).  One workgroup per column t.
 __device__ __forceinline__ void alive_column(int n_blocks, int T1, int t, const int32_t *__restrict__ alive_part, int32_t *__restrict__ alive,
@@ -3690,6 +3871,32 @@ extern "C" int rnad_bucket_indices(const rnad_tree_t *tree, int T1, int64_t B, c
                                             (const Item *)items, n_items, (const int32_t *)p.cut->bucket_path, (const int32_t *)p.cut->bucket_lo,
                                             (const int32_t *)p.cut->path_states, std::max(p.cut->max_path, 1), p.cut->n_groups, (const REL *)states,
                                             indices));
+    RNAD_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int rnad_bucket_log_stats(const rnad_tree_t *tree, int T, int64_t B, const void *states, const int32_t *items, const int32_t *n_items,
+                                     const int32_t *alive, const float *records, const float *logit_target_tab, float *row_stats, double *out,
+                                     void *stream) {
+    RNAD_REQUIRE(tree && states && items && n_items && alive && records && logit_target_tab && row_stats && out,
+                 "rnad_bucket_log_stats: null argument");
+    RNAD_REQUIRE(T >= 1 && T <= kCompactSteps && B >= 1, "rnad_bucket_log_stats: bad shape");
+    RNAD_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)row_stats & 15) == 0 && ((uintptr_t)out & 7) == 0,
+                 "rnad_bucket_log_stats: records and row_stats must be 16-byte aligned, out 8-byte aligned");
+    Plan p;
+    if (int rc = plan_for(tree, B, read_switches(), "rnad_bucket_log_stats", false, p)) return rc;
+    const BucketCut &cut = *p.cut;
+    const int tab_rows = (size_t)cut.rows * 2 * sizeof(int32_t) <= 32 * 1024 ? cut.rows : 0;  // (else every slot gathers its row's statistics)
+    hipStream_t s = (hipStream_t)stream;
+    RNAD_DISPATCH_A(tree->A, hipLaunchKernelGGL((k_log_row_stats<kA>), dim3(blocks_for(2 * tree->S)), dim3(kThreads), 0, s, 2 * tree->S, records,
+                                                logit_target_tab, row_stats, out));
+    RNAD_HIP_OK(hipGetLastError());
+    RNAD_DISPATCH_REL(p, hipLaunchKernelGGL((k_log_count<REL>), dim3((unsigned)p.max_items), dim3(kThreads), (size_t)tab_rows * 2 * sizeof(int32_t), s, T,
+                                            B, tree->S, tab_rows, cut.n_groups, (const Item *)items, n_items, (const int32_t *)cut.bucket_lo,
+                                            (const int32_t *)cut.bucket_path, (const int32_t *)cut.path_states, std::max(cut.max_path, 1),
+                                            (const REL *)states, (const float *)row_stats, out));
+    RNAD_HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_log_finish, dim3(1), dim3(64), 0, s, T, B, tree->S, alive, (const float *)row_stats, out);
     RNAD_HIP_OK(hipGetLastError());
     return 0;
 }

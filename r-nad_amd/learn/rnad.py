@@ -47,6 +47,11 @@ def _dist_on():
 
 
 class RNaD:
+    # Logged steps of the compact on-policy batch take their statistics from per-row quantities and visit counts
+    # (rnad_hip.bucket_log_stats) and read them back in ONE device -> host copy, instead of rebuilding the reference's per-slot tensors.
+    # Off by default: the logged values then stay those of the per-slot block, bit for bit.  Any other batch keeps that block anyway.
+    compact_log = False
+
     def __init__(
         self,
         tree: tree.Tree,
@@ -867,6 +872,7 @@ class RNaD:
         if norm_work is not None and not late_norm:
             norm_work.wait()
         hp = self._learn_params(alpha)
+        played = None
         if bucketed:
             # bucket-ordered batch (Episodes.generate(bucketed=True)): per-row sums in LDS, no global atomics (csrc/bucket.hip)
             records = tables.get("records")
@@ -893,6 +899,7 @@ class RNaD:
                         late_norm = True  # (the finish below; nothing to wait for when the normalisers are known)
                 else:
                     assert learned is None, "a batch whose update rode in its rollout can only be learned from as it was played"
+                    played = compact[0]  # (compact_log: the logged statistics are counted from this trajectory)
                     dlogit, dv, losses = rnad_hip.learn_bucketed_compact(self.tree.handle(), episodes.buckets, compact[0], T, records,
                                                                          tables["fast_records"], None if late_norm else norm, hp,
                                                                          want_losses=log is not None, rows=rows_now, groups=grouped)
@@ -976,7 +983,17 @@ class RNaD:
             if log is not None:
                 dist.all_reduce(losses)
 
-        if log is not None:
+        if log is not None and played is not None and getattr(self, "compact_log", False):
+            # compact_log: every logged quantity is a per-row quantity weighted with the visits of the row -- per-row statistics, the
+            # visits counted from the compact trajectory (rnad_hip.bucket_log_stats), the gradient norm as one reduction over the flat
+            # bucket, and ONE device -> host copy; nothing dense is built
+            stats = rnad_hip.bucket_log_stats(self.tree.handle(), episodes.buckets, played, T, records, logit_target)
+            grads = flat if flat is not None else torch.cat([p.grad.detach().reshape(-1) for p in self.net.parameters()])
+            total_norm = torch.linalg.vector_norm(grads, dtype=torch.float64).reshape(1)
+            host = torch.cat([stats, losses.to(torch.float64), total_norm]).tolist()
+            log.update({"loss_v": host[8], "loss_nerd": host[9], "gradient_norm": host[10]})
+            log.update(rnad_hip.log_stats_to_dict(host, T, B, A))
+        elif log is not None:
             if table is not None:
                 # the logged statistics are over per-slot tensors (rnad.py:427-452): gather them from the tables.  An absorbed
                 # slot gathers the row of state 0 -- the reference's net output there, as it evaluates the net on state 0's

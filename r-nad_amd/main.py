@@ -2,7 +2,7 @@
 R-NaD for a few values of eta on the MI355X.  Lives next to the `environment / learn / nn / util` packages, exactly like the
 reference's script lives next to its own, and uses only their reference-compatible API.
 
-    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512]
+    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log]
 """
 import argparse
 import logging
@@ -20,6 +20,8 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=100, help="learner steps per update (reference: delta_m=[100])")
     ap.add_argument("--batch", type=int, default=2**9)
     ap.add_argument("--etas", type=float, nargs="*", default=[0, 0.2, 0.5, 1])
+    ap.add_argument("--compact-log", action="store_true",
+                    help="logged steps: statistics from per-row quantities and visit counts, one host sync (RNaD.compact_log)")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
     if not torch.cuda.is_available():
@@ -57,5 +59,6 @@ if __name__ == "__main__":
             logit_clip=2,
             net_params={"type": "MLP", "max_actions": tree.max_actions, "width": 2**8},
         )
+        trial.compact_log = args.compact_log
         trial.run(log_mod=10, expl_mod=1, checkpoint_mod=args.steps)
         print(f"eta={eta}: NashConv by update:", [round(v, 3) for _, _, v in trial.nashconv_history])

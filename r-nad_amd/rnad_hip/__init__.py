@@ -1370,6 +1370,37 @@ def bucket_expand(tree, traj, records):
                                     _dp(traj.rewards, F32, "rewards"), _stream()))
 
 
+LOG_STATS = ("entropy_sum", "entropy_target_sum", "actor_learner_kld_sum", "valid", "logit_sum", "logit_min", "logit_max", "spare")
+
+
+def bucket_log_stats(tree, buckets, traj, T, records, logit_target):
+    """rnad_bucket_log_stats: the sums behind the logged statistics (rnad.py:427-452) of the first T steps of a compact trajectory played
+    with the pi columns of `records` -- per-row statistics weighted with the visits per row, counted from the 21 bytes per lane; no dense
+    buffer is built.  logit_target: the target net's logits on all 2S rows.  Returns the device tensor f64 [8] (LOG_STATS); no host sync."""
+    B, A = traj.B, tree.A
+    assert buckets.plan.B == B and traj.compact and 1 <= T <= traj.T_cap
+    assert tuple(logit_target.shape) == (2 * tree.S, A)
+    assert records.shape[0] >= 2 * tree.S and records.shape[1] == lib().rnad_bucket_record_stride(A)
+    if getattr(buckets, "alive_pending", None) is traj:
+        bucket_alive(tree, buckets)
+    complete_records(records)  # (every row's record is read)
+    row_stats = torch.empty((2 * tree.S, 8), dtype=F32, device=traj.device)
+    out = torch.empty((8,), dtype=F64, device=traj.device)
+    _check(lib().rnad_bucket_log_stats(tree.ptr, T, B, _dp(traj.states, traj.states.dtype, "states"), _dp(buckets.items, I32, "items"),
+                                       _dp(buckets.n_items, I32, "n_items"), _dp(traj.alive, I32, "alive"), _dp(records, F32, "records"),
+                                       _dp(logit_target, F32, "logit_target"), _dp(row_stats, F32, "row_stats"), _dp(out, F64, "out"),
+                                       _stream()))
+    return out
+
+
+def log_stats_to_dict(stats, T, B, A):
+    """The reference's logged keys from the host copy of bucket_log_stats' eight sums (a sequence of floats)."""
+    e, et, k, n, total, lo, hi = (float(x) for x in stats[:7])
+    mean = total / (T * B * A)
+    return {"traj_len": n / B, "logit_mean": mean, "logit_max": float("nan") if mean != mean else max(hi - mean, mean - lo),
+            "entropy": e / n, "entropy_target": et / n, "actor_learner_kld": k / n}
+
+
 def learn_bucketed_compact(tree, buckets, traj, T, records, fast_records, norm, hp, want_losses=False, rows=None, groups=None):
     """rnad_learn_bucketed_compact on the first T steps of a compact trajectory played with the pi columns of `records`;
     (records, fast_records) = bucket_records(..., fast=True).  rows: a LiveRows over the 2S rows -- only those rows of the gradient
