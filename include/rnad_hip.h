@@ -133,6 +133,33 @@ int rnad_mlp_backward_rows(int64_t max_rows, const int32_t *rows, const int64_t 
                            float *g_vb0, float *g_vw1, float *g_vb1, float *g_pw0, float *g_pb0, float *g_pw1, float *g_pb1,
                            float *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fused ConvNet  --  nn/net.py:88-269 with batch_norm=False: h = pre(obs) (a CrossConv, no relu), D residual blocks
+ * h += relu(conv1(relu(conv0(h)))), logits = policy(flatten h), value = value(flatten h).  Each CrossConv runs as two fp32-MFMA
+ * products with Toeplitz-expanded weights (csrc/conv_tower.hip); fp32 observations only.
+ *
+ * weights: HOST array of 8 + 8 D device pointers in net.parameters() order (per CrossConv: row_conv.weight [Ch,Cin,1,2A-1],
+ * row_conv.bias, col_conv.weight [Ch,Cin,2A-1,1], col_conv.bias; then policy.weight [A, Ch A^2], policy.bias, value.weight, value.bias).
+ * The packed image holds the Toeplitz operands in MFMA operand order (forward and transposed), the summed biases and the heads; pack
+ * once per weight update.  The supported query is 0 for shapes the kernels decline (Ch A not a multiple of 16, depth > 8, an
+ * activation tile beyond the LDS); the size queries then return -1.
+ *
+ * Forward: the whole tower and both heads in one launch, on all N rows (rows = n_rows = NULL) or on a row list with the
+ * semantics of the MLP's row variants (N = the list's capacity, *n_rows on the device).  A NULL output is not computed.
+ * Backward: recomputes the activations; writes (not accumulates) the gradient of every parameter, reference layouts, into ONE flat
+ * bucket `grads` of the param count's floats in net.parameters() order; dlogits [N, A], dvalue [N] are indexed like obs.  workspace:
+ * the workspace query's bytes (per-workgroup partials, reduced in a fixed order: bitwise reproducible, no float atomics).
+ * ---------------------------------------------------------------------------------------------- */
+int rnad_conv_supported(int A, int Ch, int depth);
+int64_t rnad_conv_packed_size(int A, int Ch, int depth);
+int64_t rnad_conv_param_count(int A, int Ch, int depth);
+int rnad_conv_pack(int A, int Ch, int depth, const float *const *weights, float *packed, void *stream);
+int rnad_conv_forward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                      const float *obs, float *logits, float *value, void *stream);
+int64_t rnad_conv_backward_workspace(int64_t N, int A, int Ch, int depth);
+int rnad_conv_backward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                       const float *obs, const float *dlogits, const float *dvalue, float *grads, float *workspace, void *stream);
+
 /* The legal fold.  An observation is [expected value A x A | legal mask A x A] (episode.py:62-68); on a tree whose states all have the
  * full A x A action set -- every configuration of BASELINE.json -- the legal plane is all ones in every row except the two rows of
  * the absorbing state, where it is e0 = [1, 0, ..., 0] (tree.py:133).  The first layer of nn/net.py:40-43 is then

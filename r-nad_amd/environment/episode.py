@@ -31,6 +31,10 @@ import torch
 import rnad_hip
 from environment.tree import Tree
 from nn.net import MLP as _MLP
+from nn.net import ConvNet as _ConvNet
+
+# nets whose own forward_logits is this package's fused one: their tables (or packed images) can drive the native rollouts
+_NATIVE_FORWARDS = (_MLP.forward_logits, _ConvNet.forward_logits)
 
 
 def _draw_seed():
@@ -349,7 +353,7 @@ class Episodes:
         net.eval()
         time_start = time.perf_counter()
         native = ((packed is not None or logits_table is not None or policy_table is not None) and noise_action is None
-                  and noise_chance is None and type(net).forward_logits is _MLP.forward_logits)
+                  and noise_chance is None and type(net).forward_logits in _NATIVE_FORWARDS)
         if tabular is None:
             tabular = 8 * handle.S <= T_cap * B
         tabular = native and tabular and not keep_logits
@@ -366,8 +370,7 @@ class Episodes:
             table, vtable = logits_table, value_table
             if table is None and not (bucketed and policy_table is not None):
                 packed = packed if packed is not None else net.pack()
-                table, vtable = rnad_hip.mlp_forward(packed, net.width, handle.observations_table(self.obs_half), tree.max_actions,
-                                                     want_value=store_values)
+                table, vtable = net.table_forward(packed, handle.observations_table(self.obs_half), want_value=store_values)
             defer_alive = bool(defer_alive) and compact and not trim
             self.__dict__.pop("_learned", None)
             if compact and policy_table is not None and learn is not None and visited is None and not trim:
@@ -434,7 +437,7 @@ class Episodes:
             else:
                 rnad_hip.rollout_run_tabular(handle, traj, table[:, : tree.max_actions].contiguous(), vtable if store_values else None,
                                              seed=self.seed, lane0=self.lane_offset)
-        elif native:
+        elif native and net.ROLLOUT_KERNEL:
             # the actor is this package's MLP: the whole loop is enqueued natively (rnad_rollout_run)
             packed = packed if packed is not None else net.pack()
             self.actor_logits = rnad_hip.rollout_run(handle, traj, net.width, packed, seed=self.seed, lane0=self.lane_offset,

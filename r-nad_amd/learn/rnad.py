@@ -223,7 +223,7 @@ class RNaD:
         43 KB gradient all-reduce that closes the step hands the NaN to every rank -- the failure is loud everywhere one collective later."""
         A = self.tree.max_actions
         return bool(getattr(self, "shard_rows", False) and self._dp() and self._world > 1 and log is None and not lazy and on_policy
-                    and self.batch_size <= rnad_hip.BUCKET_MAX_LANES
+                    and self.batch_size <= rnad_hip.BUCKET_MAX_LANES and self._row_extras()
                     and rnad_hip.mlp_rows_records_supported(A, self.net.width, self._fold())
                     and rnad_hip.bucket_plan(handle, local_batch) is not None)
 
@@ -233,8 +233,8 @@ class RNaD:
         tables, which the launch on the representatives leaves unwritten in every other row."""
         if not getattr(self, "dedup_rows", True) or log is not None or lazy or shard or not on_policy:
             return None
-        if not rnad_hip.mlp_rows_records_supported(self.tree.max_actions, self.net.width, fold):
-            return None
+        if self._row_extras() and not rnad_hip.mlp_rows_records_supported(self.tree.max_actions, self.net.width, fold):
+            return None  # (a net family without the fused records launch takes the two-call branch of _table_outputs on the representatives)
         d = handle.obs_dedup(getattr(self, "obs_half", False))
         return d if 5 * d.n_unique <= 4 * d.n_rows else None
 
@@ -449,14 +449,24 @@ class RNaD:
         return self._reg_identical
 
     # ------------------------------------------------------------------ tabular evaluation of the four nets
+    # The trainer asks the net what it can do (nn/net.py: MLP and ConvNet answer the same questions) instead of knowing its family.
+    def _fused_net(self):
+        """The learner net has a fused forward AND a hand-written backward over a row list: the per-row step applies."""
+        ready = getattr(self.net, "per_row_ready", None)
+        return bool(ready is not None and ready())
+
+    def _row_extras(self):
+        """The net's family also has the extras of the per-row step: the legal fold, lazy rows / the staged actor, row sharding, the
+        fused records launch (rnad_mlp_rows_records) and the one-launch optimiser tail.  Today: the MLP."""
+        return bool(getattr(self.net, "ROW_EXTRAS", False))
+
     def _fused_mlp(self):
-        A = self.tree.max_actions
-        return isinstance(self.net, net.MLP) and self.net._fusable() and rnad_hip.mlp_backward_supported(A, self.net.width)
+        return self._fused_net() and self._row_extras()
 
     def _tabular_mode(self, T, B):
         """RNaD.tabular if the tree is small enough next to a [T, B] trajectory for the table evaluation to pay, else False."""
         mode = getattr(self, "tabular", False)
-        if not mode or not self._fused_mlp():
+        if not mode or not self._fused_net():
             return False
         if getattr(self, "tabular_gate", 8) * self.tree.handle().S > T * B:
             return False
@@ -593,9 +603,8 @@ class RNaD:
         if cache["key"] != key:
             A = self.tree.max_actions
             with torch.no_grad():
-                outs = rnad_hip.mlp_forward_multi(rnad_hip.mlp_pack_many([self.net_reg._weights(), self.net_reg_._weights()], A, fold=fold),
-                                                  self.net.width, table, A,
-                                                  [(True, False), (True, False)], fold=self.tree.handle() if fold else False)
+                outs = self.net.tables_forward(type(self.net).pack_many([self.net_reg, self.net_reg_], fold=fold), table,
+                                               [(True, False), (True, False)], fold=self.tree.handle() if fold else False)
             for name, out in (("logit_reg", outs[0][0]), ("logit_reg_", outs[1][0])):
                 if cache[name] is None:
                     cache[name] = out
@@ -617,10 +626,10 @@ class RNaD:
 
     def _fold(self):
         """The table evaluations of the per-row mode use the FOLD kernels: asked for, and the tree's observation table allows it."""
-        return bool(getattr(self, "fold_legal", True)) and self.tree.handle().legal_foldable
+        return bool(getattr(self, "fold_legal", True)) and self._row_extras() and self.tree.handle().legal_foldable
 
     def _packed_images(self, fold=None):
-        """(image of net, image of net_target): the packed weight layouts the fused MLP kernels read (rnad_hip.mlp_pack), in persistent
+        """(image of net, image of net_target): the packed weight layouts the fused kernels read (the net's pack_many), in persistent
         buffers -- one pair per layout (plain / FOLD).  The pair the one-launch optimiser tail maintains (rnad_optimizer_step writes
         every new weight into the tensor AND its image slot: a training step carries no pack launch) is re-packed only when the nets'
         tensors changed as far as torch can tell (version counters, data pointers); the other pair on every request.
@@ -632,14 +641,14 @@ class RNaD:
             fold = bool(cache["maintained"])
         fold = bool(fold)
         key = tuple((id(w), w.data_ptr(), w._version) for group in ws for w in group)
-        shape = (A, self.net.width, ws[0][0].device)
+        shape = (A, type(self.net), tuple(ws[0][0].shape), len(ws[0]), ws[0][0].device)
         entry = cache["layouts"].get(fold)
         if entry is None or entry["shape"] != shape:
-            size = rnad_hip.mlp_packed_size(A, self.net.width, fold)
+            size = self.net.packed_size(fold)
             entry = cache["layouts"][fold] = {"shape": shape, "key": None,
                                               "images": [torch.empty((size,), dtype=torch.float32, device=ws[0][0].device) for _ in range(2)]}
         if entry["key"] != key or cache["maintained"] != fold:
-            rnad_hip.mlp_pack_many(list(ws), A, out=entry["images"], fold=fold)
+            type(self.net).pack_many([self.net, self.net_target], out=entry["images"], fold=fold)
             entry["key"] = key
         return entry["images"]
 
@@ -668,7 +677,8 @@ class RNaD:
             logit_reg, logit_reg_ = self._reg_tables(table, fold)
             return dict(table=table, logit=logit, v=None, logit_target=None, v_target=None, logit_reg=logit_reg, logit_reg_=logit_reg_,
                         packed_net=packed, packed_target=packed_target, staged_actor=staged_actor, fold=fold)
-        if records_hp is not None and not want_target_logits and rnad_hip.mlp_rows_records_supported(A, self.net.width, fold):
+        if (records_hp is not None and not want_target_logits and self._row_extras()
+                and rnad_hip.mlp_rows_records_supported(A, self.net.width, fold)):
             # records_hp: the caller wants the row records of this step too (rnad_hip.bucket_records(fast=True)) -- forwards and records
             # come out of ONE launch (csrc/mlp_rows.hip: a persistent workgroup per CU, a wave per hidden tile, weights in registers)
             logit_reg, logit_reg_ = self._reg_tables(table, fold)
@@ -708,15 +718,21 @@ class RNaD:
         with torch.no_grad():
             # (one launch entry per (net, head) -- three equal work units per 64-row span -- was measured: 45.5 instead of 43.4 us, every
             # workgroup loads its net's 43 KB weight image first)
-            outs = rnad_hip.mlp_forward_multi([packed, packed_target], self.net.width, table, A,
-                                              [(True, True), (want_target_logits, True)], fold=self.tree.handle() if fold else False)
+            # distinct observations without the fused records launch (ConvNet): both nets on the representatives only, their records,
+            # then every other row gets a copy of its representative's records
+            uniq = dedup.uniq if (dedup is not None and records_hp is not None) else None
+            outs = self.net.tables_forward([packed, packed_target], table, [(True, True), (want_target_logits, True)],
+                                           fold=self.tree.handle() if fold else False, live=uniq)
         logit_reg, logit_reg_ = self._reg_tables(table, fold)
         tables = dict(table=table, logit=outs[0][0], v=outs[0][1], logit_target=outs[1][0], v_target=outs[1][1], logit_reg=logit_reg,
                       logit_reg_=logit_reg_, packed_net=packed, fold=fold)
         if records_hp is not None:
             tables["records"], tables["fast_records"] = rnad_hip.bucket_records(
                 self.tree.handle(), tables["logit"], tables["v"], tables["v_target"], logit_reg, logit_reg_, records_hp,
-                step_params=step_params, fast=True)
+                step_params=step_params, fast=True, rows=uniq)
+            if uniq is not None:
+                rnad_hip.rows_expand(dedup, [tables["fast_records"], tables["records"]])
+                tables["dedup"] = dedup
         return tables
 
     def _value_tables(self, tables, visited, alpha, step_params=None):
@@ -758,7 +774,7 @@ class RNaD:
         want = getattr(self, "lazy_rows", None)
         if want is None:
             want = 2 * handle.S > local_batch
-        return bool(want and log is None and getattr(self, "compact_trajectory", True) and T_cap <= rnad_hip.COMPACT_MAX_STEPS
+        return bool(want and log is None and self._row_extras() and getattr(self, "compact_trajectory", True) and T_cap <= rnad_hip.COMPACT_MAX_STEPS
                     and self.buffer_mod == 1 and buffer.max_size == 1 and not getattr(self, "store_actor_values", False)
                     and rnad_hip.bucket_plan(handle, local_batch) is not None)
 
@@ -804,7 +820,7 @@ class RNaD:
         # and masks the absorbed ones afterwards (valid, :369).  Here the nets run on the live slots only; the others hold
         # zeros, which the same masks discard -- losses and gradients are unchanged.  Logging steps of the dense mode evaluate
         # every slot, because logit_mean / logit_max (:427-452) are taken over ALL slots.
-        fused_mlp = self._fused_mlp()
+        fused_mlp = self._fused_net()
         # Tabular evaluation (RNaD.tabular): an observation depends on (state, player to move) only, so each net is evaluated on
         # the 2S distinct observations of the tree and every (t, b) slot gathers its row (include/rnad_hip.h,
         # rnad_learn_fused_gather / rnad_learn_fused_tabular / rnad_learn_bucketed).  Worth it when the tree is small next to the
@@ -957,8 +973,8 @@ class RNaD:
                 packed, fold = self.net.pack(), False
             else:
                 packed = tables["packed_net"] if tables is not None and "packed_net" in tables else self.net.pack()  # same weights as the forward
-            rnad_hip.mlp_backward(packed, weights, backward_obs, A, dlogit.view(-1, A), dv.view(-1, 1), live=live, out=views,
-                                  fold=self.tree.handle() if fold else False, capacity=capacity)
+            self.net.backward_rows(packed, backward_obs, dlogit.view(-1, A), dv.view(-1, 1), live=live, flat=flat, views=views,
+                                   fold=self.tree.handle() if fold else False, capacity=capacity)
             if all(p_.grad is None for p_ in weights):
                 for p_, g_ in zip(weights, views):
                     p_.grad = g_

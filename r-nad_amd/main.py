@@ -2,7 +2,7 @@
 R-NaD for a few values of eta on the MI355X.  Lives next to the `environment / learn / nn / util` packages, exactly like the
 reference's script lives next to its own, and uses only their reference-compatible API.
 
-    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log]
+    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log] [--net convnet --channels 16 --depth 2]
 """
 import argparse
 import logging
@@ -22,6 +22,9 @@ if __name__ == "__main__":
     ap.add_argument("--etas", type=float, nargs="*", default=[0, 0.2, 0.5, 1])
     ap.add_argument("--compact-log", action="store_true",
                     help="logged steps: statistics from per-row quantities and visit counts, one host sync (RNaD.compact_log)")
+    ap.add_argument("--net", choices=("mlp", "convnet"), default="mlp", help="the reference's MLP line or its ConvNet line (main.py:72)")
+    ap.add_argument("--channels", type=int, default=16, help="ConvNet: channels of the CrossConv tower")
+    ap.add_argument("--depth", type=int, default=2, help="ConvNet: residual blocks")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
     if not torch.cuda.is_available():
@@ -41,6 +44,10 @@ if __name__ == "__main__":
     tree.save("small_tree")
     # tree.load("small_tree")  # instead of generate(), to reuse a tree
 
+    if args.net == "convnet":  # batch_norm=False: the fused tower and the per-row step (a BatchNorm net runs the torch modules per slot)
+        net_params = {"type": "ConvNet", "max_actions": tree.max_actions, "channels": args.channels, "depth": args.depth, "batch_norm": False}
+    else:
+        net_params = {"type": "MLP", "max_actions": tree.max_actions, "width": 2**8}
     timestamp = str(int(time()))
     for idx, eta in enumerate(args.etas):
         same_init_net = None if idx == 0 else f"{timestamp}-eta={args.etas[0]}"  # compare etas from one initial net
@@ -57,7 +64,7 @@ if __name__ == "__main__":
             gamma_averaging=0.01,
             batch_size=args.batch,
             logit_clip=2,
-            net_params={"type": "MLP", "max_actions": tree.max_actions, "width": 2**8},
+            net_params=net_params,
         )
         trial.compact_log = args.compact_log
         trial.run(log_mod=10, expl_mod=1, checkpoint_mod=args.steps)

@@ -10,9 +10,18 @@ registers (rnad_mlp_forward), with rnad_mlp_backward as its autograd backward.  
 batch, over the tree's 2S distinct observations -- instead of a Python loop over t (net.py:67).
 
 State-dict keys (`value_fc0.weight`, ...) are the reference's, so its checkpoints load unchanged.
+
+ConvNet (reference nn/net.py:88-269): the CrossConv tower with a policy and a value head.  With batch_norm=False on the GPU the
+whole tower and both heads are ONE fp32-MFMA kernel over a row list (csrc/conv_tower.hip: every CrossConv as two products with
+Toeplitz-expanded weights), with rnad_conv_backward as its autograd backward; everything else -- CPU tensors, batch_norm=True,
+non-fp32 weights, shapes rnad_conv_supported declines -- runs the plain torch modules.
+
+Both classes expose the same small interface to learn/rnad.py and environment/episode.py (per_row_ready, pack_many, packed_size,
+tables_forward, table_forward, backward_rows, ROW_EXTRAS, ROLLOUT_KERNEL), so the trainer asks the net instead of knowing its family.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 import rnad_hip
 
@@ -29,6 +38,38 @@ class MLP(nn.Module):
         self.width = width
         self._seed = int(torch.randint(0, 2**62, (1,)).item())  # sampler stream of forward(); torch.manual_seed controls it
         self._calls = 0
+
+    # ---------------------------------------------------------------- what RNaD / Episodes ask a net (ConvNet answers the same questions)
+    ROW_EXTRAS = True      # the legal fold, lazy rows, row sharding, rnad_mlp_rows_records and rnad_optimizer_step exist for this family
+    ROLLOUT_KERNEL = True  # rnad_rollout_run evaluates this net inside the native rollout loop
+
+    def per_row_ready(self):
+        """The fused forward AND backward cover this net: RNaD's per-row step (and its hand-written backward) applies."""
+        return self._fusable() and rnad_hip.mlp_backward_supported(self.max_actions, self.width)
+
+    def packed_size(self, fold=False):
+        return rnad_hip.mlp_packed_size(self.max_actions, self.width, fold)
+
+    @staticmethod
+    def pack_many(nets, out=None, fold=False):
+        """The weight images of up to four nets of one shape, in one launch."""
+        return rnad_hip.mlp_pack_many([n._weights() for n in nets], nets[0].max_actions, out=out, fold=fold)
+
+    def tables_forward(self, packed_list, table, wants, fold=False, live=None):
+        """Nets of this shape (their images) on the same observation table -> [(logits or None, value or None)], in one launch.
+        live: a row list -- the other rows are left unwritten (the multi-net launch takes one with the FOLD kernels only)."""
+        if live is None:
+            return rnad_hip.mlp_forward_multi(packed_list, self.width, table, self.max_actions, wants, fold=fold)
+        return rnad_hip.mlp_forward_multi(packed_list, self.width, table, self.max_actions, wants, fold=fold, live=live, zero_rest=False)
+
+    def table_forward(self, packed, table, want_logits=True, want_value=True, live=None, zero_rest=True):
+        return rnad_hip.mlp_forward(packed, self.width, table, self.max_actions, want_logits=want_logits, want_value=want_value, live=live,
+                                    zero_rest=zero_rest)
+
+    def backward_rows(self, packed, obs, dlogit, dv, live=None, flat=None, views=None, fold=False, capacity=None):
+        """dL/dweights for dL/dlogits, dL/dvalue on (the listed rows of) obs, written into `views` -- per-tensor views, in
+        _weights() order, of the flat bucket `flat`."""
+        return rnad_hip.mlp_backward(packed, self._weights(), obs, self.max_actions, dlogit, dv, live=live, out=views, fold=fold, capacity=capacity)
 
     # ---------------------------------------------------------------- the two perceptrons
     def _weights(self):
@@ -122,6 +163,199 @@ class MLP(nn.Module):
                     logits, value = lt.index_select(0, rows), vt.index_select(0, rows)
         if logits is None:
             logits, value = self.forward_logits(episodes.observations[:T])
+        mask_bits = getattr(episodes, "mask_bits", None)
+        if mask_bits is not None:
+            policy, log_policy = rnad_hip.policy_head(logits.detach(), mask_bits=mask_bits[:T].reshape(-1), want_log=True)
+        else:
+            policy, log_policy = rnad_hip.policy_head(logits.detach(), mask=episodes.masks[:T].reshape(-1, A).contiguous(), want_log=True)
+        return [logits.view(T, B, A), log_policy.view(T, B, A), policy.view(T, B, A), value.view(T, B, 1)]
+
+
+# ====================================================================== ConvNet (reference nn/net.py:88-269)
+def _factory(device, dtype):
+    return {"device": device, "dtype": dtype}
+
+
+class CrossConv(nn.Module):
+    """A filter shaped like a cross: one 1 x (2A-1) kernel along the board rows plus one (2A-1) x 1 kernel along the board columns,
+    each over the board zero-padded by A-1 on that axis, so every output cell sees its whole row and its whole column.
+    State-dict keys: row_conv.*, col_conv.*."""
+
+    def __init__(self, max_actions, in_channels, out_channels, device=torch.device("cpu:0"), dtype=torch.float):
+        super().__init__()
+        self.max_actions = max_actions
+        taps = 2 * max_actions - 1
+        for name, kernel in (("row_conv", (1, taps)), ("col_conv", (taps, 1))):  # registration order = state-dict order
+            self.add_module(name, nn.Conv2d(in_channels, out_channels, kernel, **_factory(device, dtype)))
+
+    def forward(self, board):
+        reach = self.max_actions - 1
+        along_rows = self.row_conv(F.pad(board, (reach, reach)))
+        along_cols = self.col_conv(F.pad(board, (0, 0, reach, reach)))
+        return along_rows + along_cols
+
+
+class ConvResBlock(nn.Module):
+    """Residual block of two CrossConvs: y = x + norm1(relu(conv1(norm0(relu(conv0(x)))))), the norm AFTER each relu; without
+    batch_norm the norms are absent from the state dict.  State-dict keys: conv0.*, conv1.*, batch_norm0.*, batch_norm1.*."""
+
+    def __init__(self, max_actions, channels, batch_norm=False, device=torch.device("cpu:0"), dtype=torch.float):
+        super().__init__()
+        for name in ("conv0", "conv1"):
+            self.add_module(name, CrossConv(max_actions, channels, channels, device, dtype))
+        for name in ("batch_norm0", "batch_norm1"):
+            self.add_module(name, nn.BatchNorm2d(channels, **_factory(device, dtype)) if batch_norm else nn.Identity())
+
+    def forward(self, x):
+        mid = self.batch_norm0(F.relu(self.conv0(x)))
+        return x + self.batch_norm1(F.relu(self.conv1(mid)))
+
+
+class ConvNet(nn.Module):
+    """Two-headed CrossConv tower: pre (CrossConv 2 -> channels, no relu), `depth` ConvResBlocks, then a policy and a value Linear on
+    the activation flattened in (c, i, j) order.  State-dict keys (pre.*, tower.<d>.*, policy.*, value.*) are the reference's."""
+
+    ROW_EXTRAS = False      # no legal fold, lazy rows, row sharding, fused records launch or fused optimiser tail for this family
+    ROLLOUT_KERNEL = False  # the native rollout loop evaluates MLPs only: a ConvNet actor is a table, or is called per step
+
+    def __init__(self, max_actions, channels, depth=1, batch_norm=True, device=torch.device("cpu:0"), dtype=torch.float):
+        super().__init__()
+        self.device, self.dtype = device, dtype
+        self.max_actions, self.channels, self.depth, self.batch_norm = max_actions, channels, depth, bool(batch_norm)
+        flat = channels * max_actions * max_actions
+        self.pre = CrossConv(max_actions, 2, channels, device, dtype)
+        self.tower = nn.ModuleList(ConvResBlock(max_actions, channels, self.batch_norm, device, dtype) for _ in range(depth))
+        self.policy = nn.Linear(flat, max_actions, **_factory(device, dtype))
+        self.value = nn.Linear(flat, 1, **_factory(device, dtype))
+        self._seed = int(torch.randint(0, 2**62, (1,)).item())  # sampler stream of forward(); torch.manual_seed controls it
+        self._calls = 0
+
+    # ---------------------------------------------------------------- the fused tower
+    def _shape(self):
+        return (self.max_actions, self.channels, self.depth)
+
+    def _weights(self):
+        """Every parameter in net.parameters() order -- the order of rnad_conv_pack and of the flat gradient bucket."""
+        return list(self.parameters())
+
+    def _fusable(self):
+        """The tower kernels cover batch_norm=False fp32 nets on the GPU whose shape rnad_conv_supported accepts.  A BatchNorm net
+        never takes them (nor any per-row table): in training mode its function depends on the batch it is given."""
+        w = self.policy.weight
+        return bool(w.is_cuda and w.dtype == torch.float32 and not self.batch_norm and rnad_hip.conv_supported(*self._shape()))
+
+    def pack(self):
+        """The packed image of the tower kernels (rnad_conv_pack), or None.  Not cached: see MLP.pack."""
+        if not self._fusable():
+            return None
+        return rnad_hip.conv_pack(self._weights(), *self._shape())
+
+    def per_row_ready(self):
+        return self._fusable()
+
+    def packed_size(self, fold=False):
+        assert not fold
+        return int(rnad_hip.lib().rnad_conv_packed_size(*self._shape()))
+
+    @staticmethod
+    def pack_many(nets, out=None, fold=False):
+        assert not fold, "the legal fold is an MLP layout"
+        outs = [None] * len(nets) if out is None else list(out)
+        return [rnad_hip.conv_pack(n._weights(), *n._shape(), out=o) for n, o in zip(nets, outs)]
+
+    def tables_forward(self, packed_list, table, wants, fold=False, live=None):
+        """Nets of this shape on the same observation table, a launch each.  live: a row list -- the other rows are left unwritten."""
+        assert not fold
+        return [rnad_hip.conv_forward(p, *self._shape(), table, want_logits=wl, want_value=wv, live=live, zero_rest=False)
+                for p, (wl, wv) in zip(packed_list, wants)]
+
+    def table_forward(self, packed, table, want_logits=True, want_value=True, live=None, zero_rest=True):
+        return rnad_hip.conv_forward(packed, *self._shape(), table, want_logits=want_logits, want_value=want_value, live=live,
+                                     zero_rest=zero_rest)
+
+    def backward_rows(self, packed, obs, dlogit, dv, live=None, flat=None, views=None, fold=False, capacity=None):
+        assert not fold
+        return rnad_hip.conv_backward(packed, self._weights(), *self._shape(), obs, dlogit, dv, live=live, out=flat, capacity=capacity)
+
+    def _tower(self, x):
+        x = self.pre(x)
+        for block in self.tower:
+            x = block(x)
+        return x.reshape(-1, self.channels * self.max_actions**2)
+
+    def forward_logits(self, input_batch, want_logits=True, want_value=True, packed=None, live=None):
+        """obs [N, 2, A, A] -> logits [N, A], value [N, 1]   (net.py:215-221,225).
+
+        Fusable nets on fp32 GPU observations: ONE HIP kernel (rnad_conv_forward); under autograd an autograd node whose backward
+        is rnad_conv_backward.  live: an rnad_hip.LiveRows over the N samples -- the kernel evaluates those rows only and returns
+        zeros elsewhere; the torch fallback ignores it and evaluates everything."""
+        A = self.max_actions
+        if input_batch.is_cuda and input_batch.dtype == torch.float32 and self._fusable():
+            obs = input_batch.contiguous()
+            packed = packed if packed is not None else self.pack()
+            if not torch.is_grad_enabled():
+                return rnad_hip.conv_forward(packed, *self._shape(), obs, want_logits, want_value, live=live)
+            if not input_batch.requires_grad:
+                return rnad_hip.FusedConv.apply(obs, self._shape(), packed, live, *self._weights())
+        x = input_batch.reshape(-1, 2, A, A)
+        if x.dtype != self.policy.weight.dtype:
+            x = x.to(self.policy.weight.dtype)
+        h = self._tower(x)
+        return (self.policy(h) if want_logits else None), (self.value(h) if want_value else None)
+
+    @staticmethod
+    def _mask(input_batch):
+        return input_batch[:, 1, :, 0].to(torch.float).contiguous()  # filter_row (net.py:214)
+
+    # ---------------------------------------------------------------- net.py:213-227
+    # (the reference takes softmax(logits) * mask, renormalised; policy_head takes where(mask, exp(logits), 0), normalised -- the same
+    # function up to rounding, and the one its own forward_batch and the MLP use)
+    @staticmethod
+    def _policy_head(logits, mask):
+        """where(mask, exp(logits), 0) / max(sum, 1e-12): rnad_policy_head on the GPU, the same expression in torch on CPU tensors."""
+        if logits.is_cuda:
+            return rnad_hip.policy_head(logits.contiguous(), mask=mask)
+        e = torch.where(mask != 0, torch.exp(logits), torch.zeros_like(logits))
+        return e / e.sum(-1, keepdim=True).clamp_min(1e-12)
+
+    def forward(self, input_batch):
+        logits, value = self.forward_logits(input_batch)
+        policy = self._policy_head(logits.detach(), self._mask(input_batch))
+        if policy.is_cuda:
+            actions = rnad_hip.sample(policy, seed=self._seed, step=self._calls & 0xFFFFFF, stream_id=2).long()
+        else:
+            actions = torch.multinomial(policy, num_samples=1).view(-1)
+        self._calls += 1
+        return logits, policy, value, actions
+
+    # ---------------------------------------------------------------- net.py:229-244
+    def forward_policy(self, input_batch: torch.Tensor) -> torch.Tensor:
+        with torch.no_grad():
+            logits, _ = self.forward_logits(input_batch, want_value=False)
+        return self._policy_head(logits, self._mask(input_batch))
+
+    # ---------------------------------------------------------------- net.py:246-269
+    def forward_batch(self, episodes):
+        """-> [logit, log_policy, policy, value], shapes [T,B,A] x3 and [T,B,1]; the contract and the table route of MLP.forward_batch
+        (the net on the tree's 2S rows when 8 S <= T B, per-slot gradients summed per row before one backward)."""
+        T, B = episodes.t_eff + 1, episodes.batch_size
+        A = self.max_actions
+        logits = value = None
+        tree = getattr(episodes, "tree", None)
+        if (tree is not None and self._fusable() and not getattr(episodes, "obs_half", False)
+                and episodes.indices.dtype == torch.int32 and episodes.indices.is_cuda and B <= 2**21):
+            handle = tree.handle()
+            if 8 * handle.S <= T * B:
+                table = handle.observations_table(False)
+                idx = episodes.indices[:T].contiguous()
+                if torch.is_grad_enabled():
+                    logits, value = rnad_hip.TabularConv.apply(table, idx, handle, self._shape(), self.pack(), *self._weights())
+                else:
+                    lt, vt = rnad_hip.conv_forward(self.pack(), *self._shape(), table)
+                    rows = (idx.long() + (torch.arange(T, device=idx.device) & 1).view(T, 1) * handle.S).reshape(-1)
+                    logits, value = lt.index_select(0, rows), vt.index_select(0, rows)
+        if logits is None:
+            logits, value = self.forward_logits(episodes.observations[:T].reshape(-1, 2, A, A))
         mask_bits = getattr(episodes, "mask_bits", None)
         if mask_bits is not None:
             policy, log_policy = rnad_hip.policy_head(logits.detach(), mask_bits=mask_bits[:T].reshape(-1), want_log=True)

@@ -571,6 +571,117 @@ class FusedMLPRows(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
+# --------------------------------------------------------------------------------------- fused ConvNet
+def conv_supported(A, Ch, depth):
+    """True when the CrossConv tower kernels (csrc/conv_tower.hip) cover the shape."""
+    return bool(lib().rnad_conv_supported(A, Ch, depth))
+
+
+def conv_param_count(A, Ch, depth):
+    return int(lib().rnad_conv_param_count(A, Ch, depth))
+
+
+def conv_pack(weights, A, Ch, depth, out=None):
+    """The ConvNet tensors (net.parameters() order, fp32, device) -> the packed image the tower kernels read (Toeplitz operands in
+    MFMA operand order, summed biases, heads).  out: a preallocated image to write into."""
+    assert len(weights) == 8 + 8 * depth
+    size = int(lib().rnad_conv_packed_size(A, Ch, depth))
+    if size < 0:
+        raise RnadHipError(f"conv_pack: unsupported shape (A={A}, channels={Ch}, depth={depth})")
+    packed = torch.empty((size,), dtype=F32, device=weights[0].device) if out is None else out
+    assert packed.numel() == size
+    wp = (C.c_void_p * len(weights))(*[_dp(w.detach(), F32, "weight").value for w in weights])
+    _check(lib().rnad_conv_pack(A, Ch, depth, wp, _dp(packed, F32, "packed"), _stream()))
+    return packed
+
+
+def conv_forward(packed, A, Ch, depth, obs, want_logits=True, want_value=True, live=None, out=None, zero_rest=True):
+    """packed: conv_pack(...); obs [N, 2, A, A] fp32 -> logits [N, A], value [N, 1] (rnad_conv_forward: tower and heads in one launch).
+    live / out / zero_rest: as mlp_forward."""
+    if obs.dtype != F32:
+        raise RnadHipError("conv_forward: fp32 observations only")
+    N = obs.numel() // (2 * A * A)
+    alloc = torch.zeros if (live is not None and zero_rest) else torch.empty
+    if out is not None:
+        logits, value = out
+        assert (logits is None or logits.shape == (N, A)) and (value is None or value.shape == (N, 1))
+    else:
+        logits = alloc((N, A), dtype=F32, device=obs.device) if want_logits else None
+        value = alloc((N, 1), dtype=F32, device=obs.device) if want_value else None
+    assert live is None or live.N == N, "live-row list built for a different batch"
+    if live is not None and live.rows.numel() == 0:  # (a list without capacity has no storage to point at: nothing is listed)
+        return logits, value
+    _check(lib().rnad_conv_forward(C.c_int64(N), *_row_list(live), A, Ch, depth, _dp(packed, F32, "packed"), _dp(obs, F32, "obs"),
+                                   _dp(logits, F32, "logits", True), _dp(value, F32, "value", True), _stream()))
+    return logits, value
+
+
+def conv_backward(packed, weights, A, Ch, depth, obs, dlogits, dvalue, live=None, out=None, capacity=None):
+    """Gradients of every ConvNet tensor for dL/dlogits [N, A], dL/dvalue [N(,1)] (rnad_conv_backward) -> views, shaped like
+    `weights`, of ONE flat bucket in net.parameters() order (out: that bucket, preallocated -- e.g. the all-reduce buffer).
+    live: a row list -- only those rows contribute.  capacity: the length of a FIXED row list (as mlp_backward)."""
+    if obs.dtype != F32:
+        raise RnadHipError("conv_backward: fp32 observations only")
+    N = obs.numel() // (2 * A * A)
+    n = conv_param_count(A, Ch, depth)
+    assert sum(w.numel() for w in weights) == n
+    flat = torch.empty((n,), dtype=F32, device=obs.device) if out is None else out
+    assert flat.numel() == n and flat.is_contiguous()
+    assert live is None or live.N == N, "live-row list built for a different batch"
+    cap = N if (capacity is None or live is None) else int(capacity)
+    if live is not None and live.rows.numel() == 0:
+        cap, live = 0, None  # (a list without capacity: no rows contribute, the gradients are zeros)
+    ws = torch.empty((max(int(lib().rnad_conv_backward_workspace(C.c_int64(cap), A, Ch, depth)) // 4, 1),), dtype=F32, device=obs.device)
+    _check(lib().rnad_conv_backward(C.c_int64(cap), *_row_list(live), A, Ch, depth, _dp(packed, F32, "packed"), _dp(obs, F32, "obs"),
+                                    _dp(dlogits, F32, "dlogits"), _dp(dvalue, F32, "dvalue"), _dp(flat, F32, "grads"),
+                                    _dp(ws, F32, "workspace"), _stream()))
+    grads, at = [], 0
+    for w in weights:
+        grads.append(flat[at:at + w.numel()].view(w.shape))
+        at += w.numel()
+    return grads
+
+
+class FusedConv(torch.autograd.Function):
+    """logits, value = FusedConv.apply(obs, shape, packed, live, *weights): rnad_conv_forward / rnad_conv_backward as one autograd
+    node.  shape = (A, Ch, depth); live: None or a row list (rows that are not listed come back as zeros and must receive zero
+    gradients); `packed` = conv_pack(weights, ...), the weights themselves only route the gradients."""
+
+    @staticmethod
+    def forward(ctx, obs, shape, packed, live, *weights):
+        ctx.shape, ctx.live = shape, live
+        ctx.save_for_backward(obs, packed, *weights)
+        return conv_forward(packed, *shape, obs, live=live)
+
+    @staticmethod
+    def backward(ctx, dlogits, dvalue):
+        obs, packed, *weights = ctx.saved_tensors
+        grads = conv_backward(packed, weights, *ctx.shape, obs, dlogits.contiguous(), dvalue.contiguous(), live=ctx.live)
+        return (None, None, None, None, *grads)
+
+
+class TabularConv(torch.autograd.Function):
+    """TabularMLP for a ConvNet: the net evaluated on the 2S rows of the tree's observation table, every slot of `indices` [T, B]
+    gathering its row; backward sums the per-slot gradients per row first (rnad_row_sums), then ONE rnad_conv_backward."""
+
+    @staticmethod
+    def forward(ctx, table, indices, tree, shape, packed, *weights):
+        T = indices.shape[0]
+        lt, vt = conv_forward(packed, *shape, table)
+        rows = (indices.long() + (torch.arange(T, device=indices.device) & 1).view(T, 1) * tree.S).reshape(-1)
+        ctx.shape, ctx.tree = shape, tree
+        ctx.save_for_backward(table, indices, packed, *weights)
+        return lt.index_select(0, rows), vt.index_select(0, rows)
+
+    @staticmethod
+    def backward(ctx, dlogits, dvalue):
+        table, indices, packed, *weights = ctx.saved_tensors
+        T, B = indices.shape
+        dl_tab, dv_tab = row_sums(ctx.tree, indices, dlogits.contiguous().view(T, B, ctx.shape[0]), dvalue.contiguous().view(T, B))
+        grads = conv_backward(packed, weights, *ctx.shape, table, dl_tab, dv_tab)
+        return (None, None, None, None, None, *grads)
+
+
 # --------------------------------------------------------------------------------------- rollout driver
 class Trajectory:
     """Preallocated [T_cap, B, ...] device buffers of one batch of episodes (struct rnad_traj)."""

@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""Benchmark of the fused ConvNet kernels (csrc/conv_tower.hip) on the BASELINE.json configs[1] tree (depth-6 ternary, 66 431 states):
+
+  (a) rnad_conv_forward (learner + target net) and rnad_conv_backward on all 2S = 132 862 observation rows and on the distinct ones,
+      with the share of the fp32-MFMA peak the executed matrix instructions reach;
+  (b) the same net as plain torch modules (nn.Conv2d / nn.Linear, autograd) on the same rows, in the same process -- the baseline;
+  (c) one default RNaD.train_step at 2^20 lanes for the ConvNet and for the MLP.
+
+    python tools/conv_bench.py [--channels 16] [--depth 2] [--reps 2000] [--rounds 3] [--lanes-log2 20] [--out FILE.md]
+
+Times are device events around `reps` back-to-back calls after a warm-up of the same shapes; fused and torch windows alternate.  Needs the GPU: there is no CPU path.
+"""
+import argparse
+import copy
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "r-nad_amd"))
+import torch  # noqa: E402
+
+import rnad_hip  # noqa: E402
+from environment.episode import Buffer  # noqa: E402
+from environment.tree import Tree  # noqa: E402
+from learn.rnad import RNaD  # noqa: E402
+from nn.net import ConvNet  # noqa: E402
+
+PEAK_F32_MFMA = 157.3e12  # MI355X fp32 matrix peak, FLOP/s
+
+
+WINDOW_MS = 500.0  # a timed window lasts about this long: well above clock and scheduler noise
+
+
+def timeit(fn, max_reps):
+    """ms per call over one window of back-to-back calls: 3 warm-up calls, one calibration call, then as many calls as fill
+    WINDOW_MS (at least 3, at most max_reps) between two device events."""
+    for _ in range(3):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    reps = int(max(3, min(max_reps, WINDOW_MS / max(a.elapsed_time(b), 1e-3))))
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def mfma_flops(A, Ch, depth):
+    """Executed MFMA flops per row: (forward, backward).  A 16x16x4 instruction is 2048 flops over 16 rows."""
+    Mt, KS, KS0 = Ch * A // 16, Ch * A // 4, (2 * A + 3) // 4
+    conv = 2 * A * Mt * KS * 128.0
+    pre = 2 * A * Mt * KS0 * 128.0
+    fwd = pre + 2 * depth * conv
+    wgrad = 2 * Mt * Mt * 4 * A * 128.0
+    wgrad_pre = 2 * Mt * 1 * 4 * A * 128.0
+    return fwd, fwd + 2 * depth * (conv + wgrad) + wgrad_pre
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--channels", type=int, default=16)
+    ap.add_argument("--depth", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=2000, help="most back-to-back calls per timed window (a window lasts about 0.5 s)")
+    ap.add_argument("--rounds", type=int, default=3, help="alternations of a fused window and a torch window")
+    ap.add_argument("--lanes-log2", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--torch-chunk", type=int, default=32768, help="rows per call of the torch modules' backward (gradients accumulate)")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--skip-torch", action="store_true", help="leave the torch-module baseline out")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "conv_bench needs the MI355X"
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    A = 3
+    tree = Tree(device=dev, max_actions=A, max_transitions=1, depth_bound=6, transition_threshold=0.0)
+    tree.generate_native(seed=0)
+    handle = tree.handle()
+    table = handle.observations_table(False)
+    dedup = handle.obs_dedup(False)
+    N = table.shape[0]
+    shape = (A, args.channels, args.depth)
+    net = ConvNet(*shape, batch_norm=False, device=dev)
+    target = copy.deepcopy(net)
+    assert net._fusable(), "this shape is declined by rnad_conv_supported: nothing to time"
+    packed, packed_t = net.pack(), target.pack()
+    dl, dv = torch.randn((N, A), device=dev), torch.randn((N, 1), device=dev)
+    fwd_flop, bwd_flop = mfma_flops(*shape)
+    title = f"# ConvNet tower kernels, A = {A}, channels = {args.channels}, depth = {args.depth}, configs[1] tree ({N} rows, {dedup.n_unique} distinct)"
+    report = {"fused": {}, "torch": {}, "steps": []}
+
+    def say(msg):
+        print(msg, flush=True)
+
+    def write_out():
+        """The report so far (rewritten after every section, so that a run that is cut short leaves what it measured)."""
+        lines = [title, "", "| what | rows | fused kernels ms | torch modules ms | speed-up | fp32-MFMA share of peak |", "|---|---|---|---|---|---|"]
+        slow = False
+        for key, (n_rows, ms, flop) in report["fused"].items():
+            base = report["torch"].get(key)
+            share = flop * n_rows / (ms * 1e-3) / PEAK_F32_MFMA
+            slow = slow or (base is not None and ms > base)
+            lines.append(f"| {key} | {n_rows} | {ms:.4f} | {'not measured' if base is None else f'{base:.4f}'} | "
+                         f"{'-' if base is None else f'{base / ms:.1f}x'} | {100 * share:.1f} % |")
+        lines += ["", f"The torch backward runs in chunks of {args.torch_chunk} rows with accumulated gradients (the convolution library's first-call "
+                  "search of backward algorithms grows with the batch: 17 s at 4 096 rows, 107 s at 32 768); its forward runs on all rows at once."]
+        lines += ["", f"| one default train_step, 2^{args.lanes_log2} lanes | ms per step | per-row step taken | hipGraph replay |", "|---|---|---|---|"]
+        lines += report["steps"]
+        if report["torch"]:
+            lines += ["", ("A fused figure above is SLOWER than the torch modules: that shape must be sent to the fallback (ConvNet._fusable / "
+                           "rnad_conv_supported)." if slow else
+                           "The fused kernels are faster than the torch modules on every line, so rnad_conv_supported keeps this shape on the fused path.")]
+        text = "\n".join(lines) + "\n"
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text)
+        return text
+
+    def torch_forward(obs):
+        with torch.no_grad():
+            for n in (net, target):
+                h = n._tower(obs)
+                n.policy(h), n.value(h)
+
+    def torch_backward(obs, gl, gv):
+        # in chunks of --torch-chunk rows, gradients accumulated: the convolution library searches its backward algorithms on the first
+        # call of every batch size, and that search grows with the batch (measured here: 17 s at 4 096 rows, 107 s at 32 768)
+        net.zero_grad(set_to_none=True)
+        for r0 in range(0, obs.shape[0], args.torch_chunk):
+            h = net._tower(obs[r0:r0 + args.torch_chunk])
+            torch.autograd.backward([net.policy(h), net.value(h)], [gl[r0:r0 + args.torch_chunk], gv[r0:r0 + args.torch_chunk]])
+
+    cases = (("all rows", None, N), ("distinct observations", dedup.uniq, dedup.n_unique))
+    # (a) the fused kernels and (b) the same net as torch modules on the same rows, ALTERNATING in rounds of `reps` calls each (the first,
+    # untimed, torch call of every shape includes the convolution library's search); the figure of a side is the mean over its rounds
+    for what, live, n_rows in cases:
+        sel = slice(None) if live is None else live.rows[:n_rows].long()
+        obs_sel, dl_sel, dv_sel = table[sel].contiguous(), dl[sel].contiguous(), dv[sel].contiguous()
+
+        def fused_forward():
+            for p in (packed, packed_t):
+                rnad_hip.conv_forward(p, *shape, table, live=live, zero_rest=False)
+
+        def fused_backward():
+            rnad_hip.conv_backward(packed, net._weights(), *shape, table, dl, dv, live=live, capacity=None if live is None else n_rows)
+
+        for kind, fused, base, flop in (("forward, net + target", fused_forward, lambda: torch_forward(obs_sel), 2 * fwd_flop),
+                                        ("backward", fused_backward, lambda: torch_backward(obs_sel, dl_sel, dv_sel), bwd_flop)):
+            key = f"{kind}, {what}"
+            ms_f, ms_t = [], []
+            for _ in range(args.rounds):
+                ms_f.append(timeit(fused, args.reps))
+                if not args.skip_torch:
+                    ms_t.append(timeit(base, args.reps))
+            report["fused"][key] = (n_rows, sum(ms_f) / len(ms_f), flop)
+            say(f"fused {key} ({n_rows} rows): {report['fused'][key][1]:.4f} ms  rounds {['%.4f' % x for x in ms_f]}")
+            if ms_t:
+                report["torch"][key] = sum(ms_t) / len(ms_t)
+                say(f"torch {key} ({n_rows} rows): {report['torch'][key]:.4f} ms  rounds {['%.4f' % x for x in ms_t]}")
+            write_out()
+    # (c) one default train_step
+    os.environ["RNAD_SAVE_DIR"] = tempfile.mkdtemp(prefix="rnad_conv_bench_")
+    B = 1 << args.lanes_log2
+    for name, params in (("ConvNet", {"type": "ConvNet", "max_actions": A, "channels": args.channels, "depth": args.depth, "batch_norm": False}),
+                         ("MLP", {"type": "MLP", "max_actions": A, "width": 256})):
+        rn = RNaD(tree=tree, device=dev, directory_name=f"bench_{name}", batch_size=B, eta=0.2, b1_adam=0.0, lr=5e-5, net_params=params)
+        rn.initialize()
+        buf = Buffer(1)
+
+        def step():
+            rn.train_step(buf, alpha=0.5)
+            rn.total_steps += 1
+
+        for _ in range(5):  # eager warm-up and the graph capture
+            step()
+        ms = timeit(step, args.steps)
+        mode = rn._tabular_mode(2 * handle.max_depth, B) is True
+        replay = bool(getattr(rn, "_graph", None) and rn._graph.get("graph") is not None)
+        report["steps"].append(f"| {name} | {ms:.4f} | {mode} | {replay} |")
+        say(f"train_step {name}: {ms:.4f} ms (per-row step {mode}, graph replay {replay})")
+        del rn, buf
+    print(write_out())
+
+
+if __name__ == "__main__":
+    main()
