@@ -148,7 +148,8 @@ int rnad_mlp_backward_rows(int64_t max_rows, const int32_t *rows, const int64_t 
  * semantics of the MLP's row variants (N = the list's capacity, *n_rows on the device).  A NULL output is not computed.
  * Backward: recomputes the activations; writes (not accumulates) the gradient of every parameter, reference layouts, into ONE flat
  * bucket `grads` of the param count's floats in net.parameters() order; dlogits [N, A], dvalue [N] are indexed like obs.  workspace:
- * the workspace query's bytes (per-workgroup partials, reduced in a fixed order: bitwise reproducible, no float atomics).
+ * the workspace query's bytes (per-workgroup partials, reduced in a fixed order: bitwise reproducible, no float atomics).  A shape whose
+ * saved activations exceed the LDS (A = 5, Ch = 16, depth = 2) recomputes them block by block instead of being declined.
  * ---------------------------------------------------------------------------------------------- */
 int rnad_conv_supported(int A, int Ch, int depth);
 int64_t rnad_conv_packed_size(int A, int Ch, int depth);
@@ -159,6 +160,13 @@ int rnad_conv_forward(int64_t N, const int32_t *rows, const int64_t *n_rows, int
 int64_t rnad_conv_backward_workspace(int64_t N, int A, int Ch, int depth);
 int rnad_conv_backward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
                        const float *obs, const float *dlogits, const float *dvalue, float *grads, float *workspace, void *stream);
+/* A tabular ACTOR on (a row list of) the tree's 2S observations, the ConvNet counterpart of rnad_mlp_forward_actor: the forward kernel
+ * itself -- logits [2S, A] and value [2S] carry the bits rnad_conv_forward gives for the same row -- whose epilogue also writes the policy
+ * rows [2S, rnad_bucket_policy_row_stride(A)] (16-byte aligned; the policy head under the mover's legal bits, zero pad columns: the table
+ * rnad_bucket_sort / rnad_bucket_play gather from with table_is_policy = 1).  A = the tree's.  rows / n_rows: both NULL = all 2S rows;
+ * rows that are not listed are neither read nor written in any output. */
+int rnad_conv_forward_actor(const rnad_tree_t *tree, const int32_t *rows, const int64_t *n_rows, int Ch, int depth, const float *packed,
+                            const float *obs, float *logits, float *value, float *policy_rows, void *stream);
 
 /* The legal fold.  An observation is [expected value A x A | legal mask A x A] (episode.py:62-68); on a tree whose states all have the
  * full A x A action set -- every configuration of BASELINE.json -- the legal plane is all ones in every row except the two rows of

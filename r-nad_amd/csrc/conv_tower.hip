@@ -26,6 +26,7 @@
 // order); one reduction kernel folds the Toeplitz diagonals and sums the workgroups in ascending order -- no float atomics, bitwise
 // reproducible.
 #include "common.hpp"
+#include "rollout_math.hpp"
 
 #include <algorithm>
 
@@ -79,6 +80,9 @@ struct ConvShape {
     __host__ __device__ size_t fwd_lds(int NT) const { return (size_t)3 * NT * 16 * P * sizeof(float); }
     // backward: H[0..D], T[0..D-1], R[0..D-2] (the last block's R lives in Gz), G, Gz, U, the observations and dL/dlogits | dL/dv
     __host__ __device__ size_t bwd_lds() const { return (size_t)16 * ((3 * D + 3) * P + XP + A + 1) * sizeof(float); }
+    // backward, LEAN (shapes whose saved activations do not fit, e.g. A = 5, Ch = 16, D = 2): H[0..D-1], one T, G, Gz, U -- H_D lives in Gz
+    // until the heads are done, relu(conv0) and relu(conv1) of a block are recomputed when the walk back reaches it
+    __host__ __device__ size_t bwd_lds_lean() const { return (size_t)16 * ((D + 4) * P + XP + A + 1) * sizeof(float); }
 };
 
 __device__ __forceinline__ int board_index(int A, int dir, int ch, int b, int x) { return dir == 0 ? (ch * A + b) * A + x : (ch * A + x) * A + b; }
@@ -128,10 +132,25 @@ __device__ __forceinline__ void cross_conv(const ConvShape &sh, const float *__r
     __syncthreads();
 }
 
-template <int NT>
+// Epilogues of k_conv_forward, after the heads of a sample tile.  FwdPlain: nothing more.  FwdActor<A> (rnad_conv_forward_actor): the net
+// is a tabular ACTOR -- the heads also park the A logits of a sample in U (free once the tower is done; sample stride P, odd: the
+// 32 samples of a half-wave sit on 32 banks for the stores here and the loads below), and one thread per sample turns them into the
+// sample's padded policy row under the mover's legal bits (net.py:225-227 as policy_head): the same function of the same logits as
+// k_policy_rows / k_row_records and the epilogue of k_mlp_forward.
+struct FwdPlain {
+    static constexpr int kA = 0;
+};
+template <int A>
+struct FwdActor {
+    static constexpr int kA = A;
+    float *__restrict__ policy_rows;        // [2S, (A + 3) & ~3], 16-byte aligned
+    const uint8_t *__restrict__ mask_tab;   // [2S]
+};
+
+template <int NT, typename Epi>
 __global__ __launch_bounds__(kConvThreads) void k_conv_forward(int64_t N, const int32_t *__restrict__ rows, const int64_t *__restrict__ n_rows,
                                                                ConvShape sh, const float *__restrict__ packed, const float *__restrict__ obs,
-                                                               float *__restrict__ logits, float *__restrict__ value) {
+                                                               float *__restrict__ logits, float *__restrict__ value, Epi epi) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (n_rows) N = *n_rows < N ? *n_rows : N;  // the list never exceeds its capacity
     constexpr int NS = NT * 16;
@@ -169,6 +188,27 @@ __global__ __launch_bounds__(kConvThreads) void k_conv_forward(int64_t N, const 
             const int64_t row = rows ? (int64_t)rows[sample] : sample;
             if (is_value) out[row] = acc;
             else out[row * A + a] = acc;
+            if constexpr (Epi::kA > 0) {
+                if (!is_value) U[s * P + a] = acc;
+            }
+        }
+        if constexpr (Epi::kA > 0) {
+            constexpr int kA = Epi::kA, PS = (kA + 3) & ~3;
+            __syncthreads();
+            for (int s = threadIdx.x; s < NS; s += kConvThreads) {
+                const int64_t sample = tile * NS + s;
+                if (sample >= N) continue;
+                const int64_t row = rows ? (int64_t)rows[sample] : sample;
+                float lg[kA], pol[PS];
+#pragma unroll
+                for (int a = 0; a < kA; ++a) lg[a] = U[s * P + a];
+                rnad::dev::policy_head_ptr<kA>(lg, epi.mask_tab[row], pol, nullptr);
+#pragma unroll
+                for (int a = kA; a < PS; ++a) pol[a] = 0.0f;
+                float4 *p4 = reinterpret_cast<float4 *>(epi.policy_rows + row * PS);
+#pragma unroll
+                for (int u = 0; u < PS / 4; ++u) p4[u] = float4{pol[4 * u], pol[4 * u + 1], pol[4 * u + 2], pol[4 * u + 3]};
+            }
         }
         __syncthreads();
     }
@@ -215,6 +255,7 @@ __device__ __forceinline__ void bias_grad(const ConvShape &sh, float *__restrict
     }
 }
 
+template <bool LEAN>
 __global__ __launch_bounds__(kConvThreads) void k_conv_backward(int64_t N, const int32_t *__restrict__ rows, const int64_t *__restrict__ n_rows,
                                                                 ConvShape sh, const float *__restrict__ packed, const float *__restrict__ obs,
                                                                 const float *__restrict__ dlogits, const float *__restrict__ dvalue,
@@ -225,8 +266,9 @@ __global__ __launch_bounds__(kConvThreads) void k_conv_backward(int64_t N, const
     const int A = sh.A, P = sh.P, XP = sh.XP, F = sh.F, D = sh.D, OBS = 2 * A * A, KA = sh.Ch * A, A1 = A + 1;
     // saved activations: H[0..D] (the residual stream), T[d] = relu(conv0), R[d] = relu(conv1) -- the last block's R is written
     // straight into Gz, where the walk back turns it into dz1 in place; gradient buffers G, Gz, U
-    float *Hs = lds, *Ts = Hs + (D + 1) * NS * P, *Rs = Ts + D * NS * P;
-    float *G = Rs + (D - 1) * NS * P, *Gz = G + NS * P, *U = Gz + NS * P, *X = U + NS * P, *DL = X + NS * XP;
+    // LEAN: H[0..D-1] and ONE T buffer; H_D is written into Gz (dead once the heads are done), T[d] and R[d] are recomputed per block
+    float *Hs = lds, *Ts = Hs + (LEAN ? D : D + 1) * NS * P, *Rs = Ts + (LEAN ? 1 : D) * NS * P;
+    float *G = LEAN ? Rs : Rs + (D - 1) * NS * P, *Gz = G + NS * P, *U = Gz + NS * P, *X = U + NS * P, *DL = X + NS * XP;
     float *__restrict__ part = workspace + (size_t)blockIdx.x * sh.part_total();
     for (int i = threadIdx.x; i < sh.part_total(); i += kConvThreads) part[i] = 0.0f;
     __syncthreads();
@@ -253,6 +295,13 @@ __global__ __launch_bounds__(kConvThreads) void k_conv_backward(int64_t N, const
         cross_conv<1>(sh, packed + sh.fwd(0), packed + sh.bias(0), sh.KS0, 2 * A, X, XP, U, [&](int s, int f, float v) { Hs[s * P + f] = v; });
         for (int d = 0; d < D; ++d) {
             const int l0 = 1 + 2 * d, l1 = 2 + 2 * d;
+            if constexpr (LEAN) {
+                float *H = Hs + d * NS * P, *Hn = d == D - 1 ? Gz : H + NS * P, *T = Ts;
+                cross_conv<1>(sh, packed + sh.fwd(l0), packed + sh.bias(l0), sh.KS, KA, H, P, T, [&](int s, int f, float v) { T[s * P + f] = fmaxf(v, 0.0f); });
+                cross_conv<1>(sh, packed + sh.fwd(l1), packed + sh.bias(l1), sh.KS, KA, T, P, U,
+                              [&](int s, int f, float v) { Hn[s * P + f] = H[s * P + f] + fmaxf(v, 0.0f); });
+                continue;
+            }
             float *H = Hs + d * NS * P, *Hn = H + NS * P, *T = Ts + d * NS * P, *R = d == D - 1 ? Gz : Rs + d * NS * P;
             cross_conv<1>(sh, packed + sh.fwd(l0), packed + sh.bias(l0), sh.KS, KA, H, P, T, [&](int s, int f, float v) { T[s * P + f] = fmaxf(v, 0.0f); });
             cross_conv<1>(sh, packed + sh.fwd(l1), packed + sh.bias(l1), sh.KS, KA, T, P, U, [&](int s, int f, float v) {
@@ -263,7 +312,7 @@ __global__ __launch_bounds__(kConvThreads) void k_conv_backward(int64_t N, const
         }
         // ---- heads: G = dL/dh_D, partials of the head weights
         {
-            const float *HD = Hs + D * NS * P;
+            const float *HD = LEAN ? Gz : Hs + D * NS * P;
             for (int idx = threadIdx.x; idx < NS * F; idx += kConvThreads) {
                 const int s = idx / F, f = idx % F;
                 float g = packed[sh.wv() + f] * DL[s * A1 + A];
@@ -287,7 +336,11 @@ __global__ __launch_bounds__(kConvThreads) void k_conv_backward(int64_t N, const
         // ---- the tower, last block first
         for (int d = D - 1; d >= 0; --d) {
             const int l0 = 1 + 2 * d, l1 = 2 + 2 * d;
-            const float *H = Hs + d * NS * P, *T = Ts + d * NS * P, *R = d == D - 1 ? Gz : Rs + d * NS * P;
+            const float *H = Hs + d * NS * P, *T = LEAN ? Ts : Ts + d * NS * P, *R = (LEAN || d == D - 1) ? Gz : Rs + d * NS * P;
+            if constexpr (LEAN) {  // relu(conv0) and relu(conv1) of this block once more: the same products, the same bits
+                cross_conv<1>(sh, packed + sh.fwd(l0), packed + sh.bias(l0), sh.KS, KA, H, P, Ts, [&](int s, int f, float v) { Ts[s * P + f] = fmaxf(v, 0.0f); });
+                cross_conv<1>(sh, packed + sh.fwd(l1), packed + sh.bias(l1), sh.KS, KA, Ts, P, U, [&](int s, int f, float v) { Gz[s * P + f] = fmaxf(v, 0.0f); });
+            }
             for (int idx = threadIdx.x; idx < NS * F; idx += kConvThreads) {
                 const int e = (idx / F) * P + idx % F;
                 Gz[e] = R[e] > 0.0f ? G[e] : 0.0f;  // dz1
@@ -394,7 +447,7 @@ int fwd_tiles(const ConvShape &sh) {
 bool conv_shape_ok(int A, int Ch, int depth) {
     if (A < 1 || A > RNAD_MAX_ACTIONS || Ch < 2 || Ch > 256 || depth < 1 || depth > kConvMaxDepth || (Ch * A) % 16 != 0) return false;
     const ConvShape sh(A, Ch, depth);
-    return fwd_tiles(sh) > 0 && sh.bwd_lds() <= kConvLds;
+    return fwd_tiles(sh) > 0 && (sh.bwd_lds() <= kConvLds || sh.bwd_lds_lean() <= kConvLds);
 }
 
 }  // namespace
@@ -420,30 +473,54 @@ extern "C" int rnad_conv_pack(int A, int Ch, int depth, const float *const *weig
     return 0;
 }
 
-extern "C" int rnad_conv_forward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
-                                 const float *obs, float *logits, float *value, void *stream) {
-    RNAD_REQUIRE(conv_shape_ok(A, Ch, depth), "rnad_conv_forward: unsupported shape (A=%d, channels=%d, depth=%d)", A, Ch, depth);
-    RNAD_REQUIRE(packed && obs && (logits || value), "rnad_conv_forward: null argument");
-    RNAD_REQUIRE(!rows == !n_rows, "rnad_conv_forward: rows and n_rows go together");
-    RNAD_REQUIRE(N >= 0, "rnad_conv_forward: negative batch");
+// One launch of k_conv_forward<NT, Epi> over N rows (or the row list), NT from fwd_tiles.
+template <typename Epi>
+static int conv_forward_launch(int64_t N, const int32_t *rows, const int64_t *n_rows, const ConvShape &sh, const float *packed, const float *obs,
+                               float *logits, float *value, Epi epi, void *stream) {
     if (N == 0) return 0;
-    const ConvShape sh(A, Ch, depth);
     const int nt = fwd_tiles(sh);
     const size_t lds = sh.fwd_lds(nt);
     const int64_t n_tiles = (N + nt * 16 - 1) / (nt * 16);
     const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, kConvFwdGrid);
-#define RNAD_CONV_FWD(NT_)                                                                                                                \
-    do {                                                                                                                                  \
-        if (lds > 64 * 1024)                                                                                                              \
-            RNAD_HIP_OK(hipFuncSetAttribute((const void *)k_conv_forward<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
-        hipLaunchKernelGGL(k_conv_forward<NT_>, dim3(grid), dim3(kConvThreads), lds, (hipStream_t)stream, N, rows, n_rows, sh, packed, obs, \
-                           logits, value);                                                                                                \
+#define RNAD_CONV_FWD(NT_)                                                                                                                  \
+    do {                                                                                                                                    \
+        auto kern = k_conv_forward<NT_, Epi>;                                                                                               \
+        if (lds > 64 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kConvThreads), lds, (hipStream_t)stream, N, rows, n_rows, sh, packed, obs, logits, value, \
+                           epi);                                                                                                            \
     } while (0)
     if (nt == 4) RNAD_CONV_FWD(4);
     else if (nt == 2) RNAD_CONV_FWD(2);
     else RNAD_CONV_FWD(1);
 #undef RNAD_CONV_FWD
     RNAD_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int rnad_conv_forward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                                 const float *obs, float *logits, float *value, void *stream) {
+    RNAD_REQUIRE(conv_shape_ok(A, Ch, depth), "rnad_conv_forward: unsupported shape (A=%d, channels=%d, depth=%d)", A, Ch, depth);
+    RNAD_REQUIRE(packed && obs && (logits || value), "rnad_conv_forward: null argument");
+    RNAD_REQUIRE(!rows == !n_rows, "rnad_conv_forward: rows and n_rows go together");
+    RNAD_REQUIRE(N >= 0, "rnad_conv_forward: negative batch");
+    return conv_forward_launch(N, rows, n_rows, ConvShape(A, Ch, depth), packed, obs, logits, value, FwdPlain{}, stream);
+}
+
+// A tabular ACTOR on (a row list of) the tree's 2S observations: rnad_conv_forward's logits and value (the same kernel, the same bits) and,
+// from its epilogue, the policy rows [2S, rnad_bucket_policy_row_stride(A)] the bucketed rollout kernels gather from.  rows / n_rows:
+// NULL = all 2S rows; rows that are not listed are neither read nor written.
+extern "C" int rnad_conv_forward_actor(const rnad_tree_t *tree, const int32_t *rows, const int64_t *n_rows, int Ch, int depth, const float *packed,
+                                       const float *obs, float *logits, float *value, float *policy_rows, void *stream) {
+    RNAD_REQUIRE(tree && packed && obs && logits && value && policy_rows, "rnad_conv_forward_actor: null argument");
+    RNAD_REQUIRE(conv_shape_ok(tree->A, Ch, depth), "rnad_conv_forward_actor: unsupported shape (A=%d, channels=%d, depth=%d)", tree->A, Ch, depth);
+    RNAD_REQUIRE(!rows == !n_rows, "rnad_conv_forward_actor: rows and n_rows go together");
+    RNAD_REQUIRE(((uintptr_t)policy_rows & 15) == 0, "rnad_conv_forward_actor: policy_rows must be 16-byte aligned");
+    const ConvShape sh(tree->A, Ch, depth);
+    RNAD_DISPATCH_A(tree->A, {
+        FwdActor<kA> epi{policy_rows, tree->mask_tab};
+        const int rc = conv_forward_launch(2 * tree->S, rows, n_rows, sh, packed, obs, logits, value, epi, stream);
+        if (rc) return rc;
+    });
     return 0;
 }
 
@@ -461,12 +538,13 @@ extern "C" int rnad_conv_backward(int64_t N, const int32_t *rows, const int64_t 
     RNAD_REQUIRE(!rows == !n_rows, "rnad_conv_backward: rows and n_rows go together");
     RNAD_REQUIRE(N >= 0, "rnad_conv_backward: negative batch");
     const ConvShape sh(A, Ch, depth);
-    const size_t lds = sh.bwd_lds();
+    const bool lean = sh.bwd_lds() > kConvLds;  // the saved activations do not fit: recompute them per block
+    const size_t lds = lean ? sh.bwd_lds_lean() : sh.bwd_lds();
     const int grid = conv_bwd_grid(N);
     hipStream_t s = (hipStream_t)stream;
-    if (lds > 64 * 1024)
-        RNAD_HIP_OK(hipFuncSetAttribute((const void *)k_conv_backward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_conv_backward, dim3(grid), dim3(kConvThreads), lds, s, N, rows, n_rows, sh, packed, obs, dlogits, dvalue, workspace);
+    auto kern = lean ? k_conv_backward<true> : k_conv_backward<false>;
+    if (lds > 64 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kConvThreads), lds, s, N, rows, n_rows, sh, packed, obs, dlogits, dvalue, workspace);
     RNAD_HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(k_conv_reduce, dim3((sh.n_params() + kConvThreads - 1) / kConvThreads), dim3(kConvThreads), 0, s, sh, grid, workspace, grads);
     RNAD_HIP_OK(hipGetLastError());

@@ -154,7 +154,8 @@ class RNaD:
         # the dense Episodes fields are written when something reads them
         self.compact_trajectory = True
         # trees that are large next to the batch (None: when 2S > lanes per rank): only the learner's policy head runs on all 2S rows;
-        # the value heads, the row records, the gradient tables and the backward cover the rows the batch visited (5 % on configs[3])
+        # the value heads, the row records, the gradient tables and the backward cover the rows the batch visited (5 % on configs[3]).
+        # A ConvNet takes this step only when asked (True); None keeps its all-rows step.
         self.lazy_rows = None
         self.last_rows = None  # rnad_hip.LiveRows of the last lazy step
         self.fused_optimizer = True  # clip + Adam + EMA target of the MLP in one launch (csrc/optim.hip) instead of ~8 torch launches
@@ -456,9 +457,15 @@ class RNaD:
         return bool(ready is not None and ready())
 
     def _row_extras(self):
-        """The net's family also has the extras of the per-row step: the legal fold, lazy rows / the staged actor, row sharding, the
-        fused records launch (rnad_mlp_rows_records) and the one-launch optimiser tail.  Today: the MLP."""
+        """The net's family also has the extras of the per-row step: the legal fold, row sharding, the fused records launch
+        (rnad_mlp_rows_records) and the one-launch optimiser tail.  Today: the MLP.  (Lazy rows are asked for separately: _lazy_rows_ready.)"""
         return bool(getattr(self.net, "ROW_EXTRAS", False))
+
+    def _lazy_rows_ready(self):
+        """The net's family has a staged actor for the lazy-rows step (nn/net.py lazy_rows_ready).  A family without the other extras of the
+        per-row step (row sharding among them) keeps the all-rows step under data parallel."""
+        ready = getattr(self.net, "lazy_rows_ready", None)
+        return bool(ready is not None and ready() and (self._row_extras() or not self._dp()))
 
     def _fused_mlp(self):
         return self._fused_net() and self._row_extras()
@@ -666,16 +673,16 @@ class RNaD:
             # lazy rows: the learner's policy head is evaluated in stages by the rollout (staged_actor below: the upper rows of the cut,
             # then the rows of the groups the batch descends into); rows no lane can reach stay uninitialised and are never read
             logit = torch.empty((table.shape[0], A), dtype=torch.float32, device=table.device)
-            # the actor's policy rows come out of the same launch as its logits (rnad_mlp_forward_actor): the rollout kernels gather from them
+            # the actor's policy rows come out of the same launch as its logits (rnad_mlp_forward_actor / rnad_conv_forward_actor): the
+            # rollout kernels gather from them
             logit._policy_rows = torch.empty((table.shape[0], int(rnad_hip.lib().rnad_bucket_policy_row_stride(A))), dtype=torch.float32,
                                              device=table.device)
-
-            def staged_actor(rows, packed=packed, logit=logit, table=table, width=self.net.width, fold=self.tree.handle() if fold else False):
-                with torch.no_grad():
-                    rnad_hip.mlp_forward_actor(self.tree.handle(), packed, width, table, logit, logit._policy_rows, rows=rows, fold=fold)
-
+            # a net with one tower under both heads leaves the learner's value there too: every row the batch can visit is staged
+            v = (torch.empty((table.shape[0], 1), dtype=torch.float32, device=table.device)
+                 if getattr(self.net, "ACTOR_WRITES_VALUE", False) else None)
+            staged_actor = self.net.staged_actor(self.tree.handle(), packed, table, logit, v, logit._policy_rows, fold=fold)
             logit_reg, logit_reg_ = self._reg_tables(table, fold)
-            return dict(table=table, logit=logit, v=None, logit_target=None, v_target=None, logit_reg=logit_reg, logit_reg_=logit_reg_,
+            return dict(table=table, logit=logit, v=v, logit_target=None, v_target=None, logit_reg=logit_reg, logit_reg_=logit_reg_,
                         packed_net=packed, packed_target=packed_target, staged_actor=staged_actor, fold=fold)
         if (records_hp is not None and not want_target_logits and self._row_extras()
                 and rnad_hip.mlp_rows_records_supported(A, self.net.width, fold)):
@@ -740,6 +747,17 @@ class RNaD:
         tables and the backward on the rows the batch visited -- `visited` int32 [2S] from the rollout, compacted on the stream."""
         handle, A = self.tree.handle(), self.tree.max_actions
         rows = rnad_hip.compact_valid(visited)
+        if getattr(self.net, "ACTOR_WRITES_VALUE", False):
+            # one tower under both heads: the staged actor launches wrote the learner's value on every row they evaluated, and a visited
+            # row is a staged row -- only the target's value head is still to come
+            with torch.no_grad():
+                tables["v_target"] = self.net.tables_forward([tables["packed_target"]], tables["table"], [(False, True)], live=rows)[0][1]
+            tables["records"], tables["fast_records"] = rnad_hip.bucket_records(
+                handle, tables["logit"], tables["v"], tables["v_target"], tables["logit_reg"], tables["logit_reg_"], self._learn_params(alpha),
+                step_params=step_params, fast=True, rows=rows)
+            tables["rows"] = rows
+            self.last_rows = rows
+            return tables
         if rnad_hip.mlp_rows_records_supported(A, self.net.width, tables.get("fold", False), True):
             # both value heads on the listed rows and their records in one launch (csrc/mlp_rows.hip, the variant that reads the logits)
             with torch.no_grad():
@@ -772,9 +790,9 @@ class RNaD:
 
     def _use_lazy_rows(self, handle, local_batch, T_cap, log, buffer):
         want = getattr(self, "lazy_rows", None)
-        if want is None:
-            want = 2 * handle.S > local_batch
-        return bool(want and log is None and self._row_extras() and getattr(self, "compact_trajectory", True) and T_cap <= rnad_hip.COMPACT_MAX_STEPS
+        if want is None:  # (a family without the automatic rule keeps the all-rows step unless asked)
+            want = getattr(self.net, "LAZY_ROWS_AUTO", False) and 2 * handle.S > local_batch
+        return bool(want and log is None and self._lazy_rows_ready() and getattr(self, "compact_trajectory", True) and T_cap <= rnad_hip.COMPACT_MAX_STEPS
                     and self.buffer_mod == 1 and buffer.max_size == 1 and not getattr(self, "store_actor_values", False)
                     and rnad_hip.bucket_plan(handle, local_batch) is not None)
 

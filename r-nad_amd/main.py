@@ -2,7 +2,7 @@
 R-NaD for a few values of eta on the MI355X.  Lives next to the `environment / learn / nn / util` packages, exactly like the
 reference's script lives next to its own, and uses only their reference-compatible API.
 
-    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log] [--net convnet --channels 16 --depth 2]
+    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log] [--net convnet --channels 16 --depth 2 [--lazy-rows]]
 """
 import argparse
 import logging
@@ -25,6 +25,8 @@ if __name__ == "__main__":
     ap.add_argument("--net", choices=("mlp", "convnet"), default="mlp", help="the reference's MLP line or its ConvNet line (main.py:72)")
     ap.add_argument("--channels", type=int, default=16, help="ConvNet: channels of the CrossConv tower")
     ap.add_argument("--depth", type=int, default=2, help="ConvNet: residual blocks")
+    ap.add_argument("--lazy-rows", action="store_true",
+                    help="RNaD.lazy_rows = True: the nets run on the rows the batch stages and visits (a ConvNet's opt-in; automatic for the MLP)")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
     if not torch.cuda.is_available():
@@ -67,5 +69,7 @@ if __name__ == "__main__":
             net_params=net_params,
         )
         trial.compact_log = args.compact_log
+        if args.lazy_rows:
+            trial.lazy_rows = True
         trial.run(log_mod=10, expl_mod=1, checkpoint_mod=args.steps)
         print(f"eta={eta}: NashConv by update:", [round(v, 3) for _, _, v in trial.nashconv_history])

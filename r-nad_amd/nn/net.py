@@ -17,7 +17,8 @@ Toeplitz-expanded weights), with rnad_conv_backward as its autograd backward; ev
 non-fp32 weights, shapes rnad_conv_supported declines -- runs the plain torch modules.
 
 Both classes expose the same small interface to learn/rnad.py and environment/episode.py (per_row_ready, pack_many, packed_size,
-tables_forward, table_forward, backward_rows, ROW_EXTRAS, ROLLOUT_KERNEL), so the trainer asks the net instead of knowing its family.
+tables_forward, table_forward, backward_rows, ROW_EXTRAS, ROLLOUT_KERNEL; for lazy rows: lazy_rows_ready, LAZY_ROWS_AUTO, staged_actor,
+ACTOR_WRITES_VALUE), so the trainer asks the net instead of knowing its family.
 """
 import torch
 import torch.nn as nn
@@ -40,12 +41,29 @@ class MLP(nn.Module):
         self._calls = 0
 
     # ---------------------------------------------------------------- what RNaD / Episodes ask a net (ConvNet answers the same questions)
-    ROW_EXTRAS = True      # the legal fold, lazy rows, row sharding, rnad_mlp_rows_records and rnad_optimizer_step exist for this family
+    ROW_EXTRAS = True      # the legal fold, row sharding, rnad_mlp_rows_records and rnad_optimizer_step exist for this family
     ROLLOUT_KERNEL = True  # rnad_rollout_run evaluates this net inside the native rollout loop
+    LAZY_ROWS_AUTO = True  # RNaD.lazy_rows = None: lazy rows whenever the tree has more rows than the rank plays lanes
+    ACTOR_WRITES_VALUE = False  # separate heads: the staged actor is the policy head alone, the value head runs on the visited rows later
 
     def per_row_ready(self):
         """The fused forward AND backward cover this net: RNaD's per-row step (and its hand-written backward) applies."""
         return self._fusable() and rnad_hip.mlp_backward_supported(self.max_actions, self.width)
+
+    def lazy_rows_ready(self):
+        """The family has a staged actor (rnad_mlp_forward_actor): RNaD's lazy-rows step applies."""
+        return True
+
+    def staged_actor(self, handle, packed, table, logit, v, policy_rows, fold=False):
+        """The closure Episodes.generate(staged_actor=...) calls with row lists: this net's policy head (image `packed`) on those rows of
+        the tree's observation `table` -> `logit` and `policy_rows` (v: not written, see ACTOR_WRITES_VALUE).  fold: the FOLD image."""
+        fold = handle if fold else False
+
+        def staged_actor(rows, packed=packed, logit=logit, table=table, width=self.width, fold=fold):
+            with torch.no_grad():
+                rnad_hip.mlp_forward_actor(handle, packed, width, table, logit, policy_rows, rows=rows, fold=fold)
+
+        return staged_actor
 
     def packed_size(self, fold=False):
         return rnad_hip.mlp_packed_size(self.max_actions, self.width, fold)
@@ -215,8 +233,10 @@ class ConvNet(nn.Module):
     """Two-headed CrossConv tower: pre (CrossConv 2 -> channels, no relu), `depth` ConvResBlocks, then a policy and a value Linear on
     the activation flattened in (c, i, j) order.  State-dict keys (pre.*, tower.<d>.*, policy.*, value.*) are the reference's."""
 
-    ROW_EXTRAS = False      # no legal fold, lazy rows, row sharding, fused records launch or fused optimiser tail for this family
+    ROW_EXTRAS = False      # no legal fold, row sharding, fused records launch or fused optimiser tail for this family
     ROLLOUT_KERNEL = False  # the native rollout loop evaluates MLPs only: a ConvNet actor is a table, or is called per step
+    LAZY_ROWS_AUTO = False  # lazy rows are opt-in for this family (RNaD.lazy_rows = True): None keeps the all-rows step
+    ACTOR_WRITES_VALUE = True  # one tower under both heads: the staged actor launches leave the learner's value on every row they evaluate
 
     def __init__(self, max_actions, channels, depth=1, batch_norm=True, device=torch.device("cpu:0"), dtype=torch.float):
         super().__init__()
@@ -252,6 +272,22 @@ class ConvNet(nn.Module):
 
     def per_row_ready(self):
         return self._fusable()
+
+    def lazy_rows_ready(self):
+        """The staged actor (rnad_conv_forward_actor) covers this net: RNaD's lazy-rows step applies when asked for."""
+        return self._fusable()
+
+    def staged_actor(self, handle, packed, table, logit, v, policy_rows, fold=False):
+        """The closure Episodes.generate(staged_actor=...) calls with row lists: tower and both heads (image `packed`) on those rows of
+        the tree's observation `table` -> `logit`, `v` and `policy_rows`, one launch per list."""
+        assert not fold and v is not None
+        shape = self._shape()
+
+        def staged_actor(rows):
+            with torch.no_grad():
+                rnad_hip.conv_forward_actor(handle, packed, *shape, table, logit, v, policy_rows, rows=rows)
+
+        return staged_actor
 
     def packed_size(self, fold=False):
         assert not fold

@@ -616,6 +616,22 @@ def conv_forward(packed, A, Ch, depth, obs, want_logits=True, want_value=True, l
     return logits, value
 
 
+def conv_forward_actor(tree, packed, A, Ch, depth, obs, logits, value, policy_rows, rows=None):
+    """rnad_conv_forward_actor: the ConvNet on (the listed rows of) the tree's observation table -> `logits` [2S, A] and `value` [2S, 1] (the
+    bits of conv_forward) and, from the kernel's epilogue, `policy_rows` [2S, policy row stride] -- the actor table of bucket_sort /
+    bucket_play(table_is_policy=True).  Rows that are not listed are left alone in all three."""
+    if obs.dtype != F32:
+        raise RnadHipError("conv_forward_actor: fp32 observations only")
+    N = 2 * tree.S
+    assert A == tree.A and obs.numel() == N * 2 * A * A
+    assert logits.shape == (N, A) and value.numel() == N and policy_rows.shape[0] == N
+    assert rows is None or rows.N == N
+    if rows is not None and rows.rows.numel() == 0:  # (a list without capacity has no storage to point at: nothing is listed)
+        return
+    _check(lib().rnad_conv_forward_actor(tree.ptr, *_row_list(rows), Ch, depth, _dp(packed, F32, "packed"), _dp(obs, F32, "obs"),
+                                         _dp(logits, F32, "logits"), _dp(value, F32, "value"), _dp(policy_rows, F32, "policy_rows"), _stream()))
+
+
 def conv_backward(packed, weights, A, Ch, depth, obs, dlogits, dvalue, live=None, out=None, capacity=None):
     """Gradients of every ConvNet tensor for dL/dlogits [N, A], dL/dvalue [N(,1)] (rnad_conv_backward) -> views, shaped like
     `weights`, of ONE flat bucket in net.parameters() order (out: that bucket, preallocated -- e.g. the all-reduce buffer).

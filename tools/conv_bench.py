@@ -8,6 +8,10 @@
 
     python tools/conv_bench.py [--channels 16] [--depth 2] [--reps 2000] [--rounds 3] [--lanes-log2 20] [--out FILE.md]
 
+--lazy runs another leg instead (default --out profiles/convnet_lazy_rows.md): one default ConvNet train_step with RNaD.lazy_rows off (the
+all-rows step) and on (staged actor, target and backward on the visited rows), on the pruned 5x5, 4-outcome configs[3]-shaped tree and on
+the configs[1] tree, with the rows each step ran on.  The two trainers of a tree start from the same seed; their windows alternate.
+
 Times are device events around `reps` back-to-back calls after a warm-up of the same shapes; fused and torch windows alternate.  Needs the GPU: there is no CPU path.
 """
 import argparse
@@ -63,6 +67,69 @@ def mfma_flops(A, Ch, depth):
     return fwd, fwd + 2 * depth * (conv + wgrad) + wgrad_pre
 
 
+def lazy_leg(args, dev):
+    """One default ConvNet train_step with lazy_rows off and on, per tree: ms per step (mean and spread over alternating windows) and the
+    rows the actor / the target and the backward ran on."""
+    os.environ["RNAD_SAVE_DIR"] = tempfile.mkdtemp(prefix="rnad_conv_lazy_")
+    B = 1 << args.lanes_log2
+    out = args.out or os.path.join(ROOT, "profiles", "convnet_lazy_rows.md")
+    lines = [f"# ConvNet train_step with lazy rows off / on, channels = {args.channels}, depth = {args.depth}, 2^{args.lanes_log2} lanes", "",
+             f"Device events around back-to-back steps; every window lasts about {WINDOW_MS / 1000:g} s after 8 priming steps of its trainer (eager warm-up "
+             f"and the graph capture); the windows of the two trainers alternate, {args.rounds} rounds; a figure is the mean over the rounds, with the "
+             "smallest and the largest round beside it.", "",
+             "| tree | 2S rows | lazy_rows | ms per step (min .. max) | actor rows (staged_rows) | target + backward rows (last_rows) | hipGraph replay |",
+             "|---|---|---|---|---|---|---|"]
+    trees = (("configs[3] shape: 5x5, 4 outcomes, depth 8, threshold 0.1, pruned 7/8", dict(max_actions=5, max_transitions=4, depth_bound=8, transition_threshold=0.1), (7, 8)),
+             ("configs[1]: 3x3, depth 6", dict(max_actions=3, max_transitions=1, depth_bound=6, transition_threshold=0.0), (0, 0)))
+    ratios = []
+    for what, kw, prune in trees:
+        tree = Tree(device=dev, **kw)
+        tree.generate_native(seed=0, prune=prune)
+        handle = tree.handle()
+        A, S2 = tree.max_actions, 2 * handle.S
+        legs = {}
+        for lazy in (False, True):
+            torch.manual_seed(0)
+            rn = RNaD(tree=tree, device=dev, directory_name=f"lazy_{A}_{lazy}", batch_size=B, eta=0.2, b1_adam=0.0, lr=5e-5,
+                      net_params={"type": "ConvNet", "max_actions": A, "channels": args.channels, "depth": args.depth, "batch_norm": False})
+            rn.initialize()
+            rn.lazy_rows = lazy
+            buf = Buffer(1)
+
+            def step(rn=rn, buf=buf):
+                rn.train_step(buf, alpha=0.5)
+                rn.total_steps += 1
+
+            for _ in range(8):
+                step()
+            torch.cuda.synchronize()
+            legs[lazy] = (rn, step, [])
+        for _ in range(args.rounds):
+            for lazy in (False, True):
+                legs[lazy][2].append(timeit(legs[lazy][1], args.steps))
+        for lazy in (False, True):
+            rn, _, ms = legs[lazy]
+            staged = getattr(rn.last_episodes, "staged_rows", None) if lazy else None
+            took = staged is not None
+            actor = "+".join(str(int(r.count.item())) for r in staged) if took else str(S2)
+            visited = int(rn.last_rows.count.item()) if (took and rn.last_rows is not None) else S2
+            replay = bool(getattr(rn, "_graph", None) and rn._graph.get("graph") is not None)
+            mean = sum(ms) / len(ms)
+            lines.append(f"| {what} | {S2} | {'on' if lazy else 'off'}{'' if took == lazy else ' (NOT TAKEN)'} | {mean:.3f} ({min(ms):.3f} .. {max(ms):.3f}) | "
+                         f"{actor} | {visited} | {replay} |")
+            print(lines[-1], flush=True)
+        off, on = (sum(legs[k][2]) / len(legs[k][2]) for k in (False, True))
+        ratios.append(f"- {what}: all-rows step / lazy step = {off / on:.2f}x ({off:.3f} ms / {on:.3f} ms).")
+        legs.clear()
+        del tree, handle
+        torch.cuda.empty_cache()
+    lines += ["", "`lazy_rows` off is the step of the commit before this leg existed (every net on all 2S rows); the ratio against it:", ""] + ratios
+    text = "\n".join(lines) + "\n"
+    with open(out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", type=int, default=16)
@@ -74,9 +141,12 @@ def main():
     ap.add_argument("--torch-chunk", type=int, default=32768, help="rows per call of the torch modules' backward (gradients accumulate)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-torch", action="store_true", help="leave the torch-module baseline out")
+    ap.add_argument("--lazy", action="store_true", help="only the lazy-rows leg: a ConvNet train_step with lazy_rows off and on, on two trees")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "conv_bench needs the MI355X"
     dev = torch.device("cuda:0")
+    if args.lazy:
+        return lazy_leg(args, dev)
     torch.manual_seed(0)
     A = 3
     tree = Tree(device=dev, max_actions=A, max_transitions=1, depth_bound=6, transition_threshold=0.0)
