@@ -644,6 +644,9 @@ int rnad_mlp_rows_records_supported(int A, int W, int fold, int policy_from_tabl
 /* rnad_mlp_rows_actor: rnad_mlp_forward_actor with the mapping of csrc/mlp_rows.hip (weights in registers, a wave per hidden tile) -- the
  * three staging launches of a large tree's actor, each on a short row list.  Same outputs up to the order of the second-layer sums. */
 int rnad_mlp_rows_actor_supported(int A, int W, int fold);
+/* The split-precision first layer of the launches above (mode 0: records, 1: records with policy_from_table, 2: actor) on a supported
+ * shape: 0 = never, 1 = only with RNAD_MLP_SPLIT=1, 2 = by default.  The launch selects its kernel by this function alone. */
+int rnad_mlp_rows_uses_split(int A, int W, int fold, int mode);
 int rnad_mlp_rows_actor(const rnad_tree_t *tree, const int32_t *rows, const int64_t *n_rows, int W, int fold, const float *packed, const void *obs,
                         int obs_half, float *logits, float *policy_rows, void *stream);
 int rnad_mlp_rows_records(const rnad_tree_t *tree, int W, int fold, const float *packed_net, const float *packed_target, const void *obs,

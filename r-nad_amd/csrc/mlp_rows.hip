@@ -79,7 +79,8 @@ __device__ __forceinline__ void chain_reg(const float (&a)[KS], const float *__r
 // float), and W x as SIX v_mfma_f32_32x32x16_bf16 products per 16 input features -- W_l x_h, W_h x_l, W_m x_m, W_m x_h, W_h x_m, W_h x_h,
 // small terms first -- accumulated in fp32 by the matrix core.  Every bf16 x bf16 product is exact in fp32; what is dropped (W_m x_l,
 // W_l x_m, W_l x_l) is below 2^-24 |W| |x| in total, i.e. below the rounding of the fp32 chain it replaces: the same function to fp32
-// accuracy in another summation order (tests/test_hip_rows.py: 1e-5 / 3e-6 against k_mlp_forward as before).  6 x 32 cycles per 16
+// accuracy in another summation order (tests/test_hip_rows_shapes.py: every instantiation against the net in fp64, within 8 x 2^-24 of the
+// sum of the absolute terms; tests/test_rows_shapes.py: leaving out any one of the three small products costs 28 - 48 x 2^-24).  6 x 32 cycles per 16
 // features against 8 x 64 (A = 3 with the fold: 5 x 64), and the bf16 matrix pipe leaves the VALU free for the epilogues.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -532,6 +533,17 @@ extern "C" int rnad_mlp_rows_actor_supported(int A, int W, int fold) {
     return A <= (fold ? 5 : 3);
 }
 
+// The split first layer (chain_split on rows staged in LDS) of a supported shape: 0 = no such launch (no fold, A outside 2 .. 5, a width
+// below 256, or the staged rows do not fit the LDS), 1 = only where RNAD_MLP_SPLIT=1 asks for it, 2 = the default (first layers of more than
+// 16 input features).  mode: 0 = both nets and the records, 1 = logits from the table, 2 = the staged actor.  rows_launch selects by this
+// and nothing else, so tests/test_rows_shapes.py can name every instantiation that can be launched.
+extern "C" int rnad_mlp_rows_uses_split(int A, int W, int fold, int mode) {
+    if (mode < 0 || mode > 2 || A < 2 || A > 5 || !fold || W != kRowsMaxWaves * kTile) return 0;
+    if (rows_lds_bytes(A, W, mode, fold, true) > 160 * 1024) return 0;
+    const int K_in = (A * A + 2) & ~1;
+    return (K_in + 15) / 16 > 1 ? 2 : 1;
+}
+
 static int rows_launch(const rnad_tree_t *tree, int W, int fold, const void *obs, int obs_half, int mode, const RowsArgs &g,
                        const rnad_learn_params_t &hp, hipStream_t stream) {
     const int A = tree->A, T = W / kTile;
@@ -548,10 +560,8 @@ static int rows_launch(const rnad_tree_t *tree, int W, int fold, const void *obs
     // A = 3 it is a tie on all 132 862 rows of configs[1] (44.7 against 45.4 us) and a loss on the 13 676 distinct ones (13.7 against 11.8:
     // one step per workgroup, all prologue), so the default step of configs[1] keeps the r05 kernel.
     const char *split_e = getenv("RNAD_MLP_SPLIT");
-    const int K_in = fold ? ((A * A + 2) & ~1) : 2 * A * A;
-    const bool split_wanted = split_e ? atoi(split_e) != 0 : (K_in + 15) / 16 > 1;
-    const bool split = split_wanted && A >= 2 && A <= 5 && fold && T == kRowsMaxWaves &&
-                       rows_lds_bytes(A, W, mode, fold, true) <= 160 * 1024;
+    const int can_split = rnad_mlp_rows_uses_split(A, W, fold, mode);
+    const bool split = split_e ? (atoi(split_e) != 0 && can_split != 0) : can_split == 2;
     const size_t lds_bytes = rows_lds_bytes(A, W, mode, fold, split);
 #define RNAD_ROWS_LAUNCH4(T_, F_, M_, S_)                                                                                              \
     do {                                                                                                                               \

@@ -1653,12 +1653,14 @@ def mlp_rows_records_supported(A, W, fold=False, from_table=False):
 
 
 def mlp_rows_records(tree, packed_net, packed_target, W, obs, logit_reg_tab, logit_reg_tab_, hp, step_params=None, fold=False, rows=None,
-                     logit_tab=None, want_records=True, want_policy_rows=True, alloc_rows=None):
+                     logit_tab=None, want_records=True, want_policy_rows=True, alloc_rows=None, out=None):
     """rnad_mlp_rows_records: learner (both heads) and target (value head) on the tree's observation table `obs` AND the row records of
     bucket_records(fast=True), in one launch.  Returns dict(logit [2S, A], v [2S, 1], v_target [2S, 1], records, fast_records); the
     actor's policy rows travel as records._policy_rows, as with bucket_records.
     logit_tab: the learner's logits already exist (a staged actor wrote them) -- only the value heads are evaluated; rows: a LiveRows
-    over the 2S rows -- only those rows are evaluated and written (policy rows are then not produced: only a full table can be an actor)."""
+    over the 2S rows -- only those rows are evaluated and written (policy rows are then not produced: only a full table can be an actor).
+    out: dict of existing tables to write into, any of logit / v / v_target / records / fast_records / policy_rows (fp32, contiguous, the
+    shapes below): a table that is given is not allocated, and its rows that are not listed are left alone."""
     fold = _fold_checked(fold, obs, "mlp_rows_records")
     A, N = tree.A, 2 * tree.S
     assert obs.numel() == N * 2 * A * A, "mlp_rows_records: obs must be the tree's observation table"
@@ -1670,14 +1672,26 @@ def mlp_rows_records(tree, packed_net, packed_target, W, obs, logit_reg_tab, log
     # never written); with it the policy rows are produced for a row list too
     M = N if alloc_rows is None else int(alloc_rows)
     assert M >= N
-    logit = logit_tab if from_table else torch.empty((M, A), dtype=F32, device=dev)
-    v = torch.empty((M, 1), dtype=F32, device=dev)
-    vt = torch.empty((M, 1), dtype=F32, device=dev)
-    rec = torch.empty((M, int(lib().rnad_bucket_record_stride(A))), dtype=F32, device=dev) if want_records else None
-    quick = torch.empty((M, int(lib().rnad_bucket_fast_record_stride(A))), dtype=F32, device=dev)
-    pol = (torch.empty((M, int(lib().rnad_bucket_policy_row_stride(A))), dtype=F32, device=dev)
-           if (want_policy_rows and (rows is None or alloc_rows is not None) and not from_table and os.environ.get("RNAD_POLICY_ROWS", "1") == "1")
+    out = dict(out or {})
+    assert not (from_table and "logit" in out), "mlp_rows_records: logit_tab is the logit table"
+
+    def table(key, cols):
+        t = out.pop(key, None)
+        if t is None:
+            return torch.empty((M, cols), dtype=F32, device=dev)
+        assert t.shape == (M, cols), f"mlp_rows_records: out[{key!r}] must be [{M}, {cols}]"
+        return t
+
+    logit = logit_tab if from_table else table("logit", A)
+    v = table("v", 1)
+    vt = table("v_target", 1)
+    rec = table("records", int(lib().rnad_bucket_record_stride(A))) if (want_records or "records" in out) else None
+    quick = table("fast_records", int(lib().rnad_bucket_fast_record_stride(A)))
+    pol = (table("policy_rows", int(lib().rnad_bucket_policy_row_stride(A)))
+           if ("policy_rows" in out and not from_table) or
+              (want_policy_rows and (rows is None or alloc_rows is not None) and not from_table and os.environ.get("RNAD_POLICY_ROWS", "1") == "1")
            else None)
+    assert not out, f"mlp_rows_records: unknown or unused out tables {sorted(out)}"
     _check(lib().rnad_mlp_rows_records(tree.ptr, W, int(fold), _dp(packed_net, F32, "packed_net"), _dp(packed_target, F32, "packed_target"),
                                        _dp(obs, F16 if half else F32, "obs"), int(half), *_row_list(rows), int(from_table),
                                        _dp(logit, F32, "logit_tab"), _dp(v, F32, "v_tab"), _dp(vt, F32, "v_target_tab"),
