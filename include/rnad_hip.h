@@ -116,6 +116,10 @@ int64_t rnad_mlp_backward_workspace(int64_t N, int A, int W);
 int rnad_mlp_backward(int64_t N, int A, int W, const float *packed, const void *obs, int obs_half, const float *dlogits,
                       const float *dvalue, float *g_vw0, float *g_vb0, float *g_vw1, float *g_vb1, float *g_pw0,
                       float *g_pb0, float *g_pw1, float *g_pb1, float *workspace, void *stream);
+/* The launch rnad_mlp_backward (fold != 0: rnad_mlp_backward_fold) gives N rows (or a row list of capacity N) on the current device, for
+ * tests that size a case from it; host code only.  out [4]: waves per workgroup, groups of hidden tiles (grid y; waves * groups = W / 32),
+ * persistent workgroups (grid x = rows of per-workgroup partials that the reduction sums), 1 if the register-resident kernel runs. */
+int rnad_mlp_backward_plan(int64_t N, int A, int W, int fold, int32_t *out);
 
 /* Ragged trees: once an episode is absorbed (state 0) the reference keeps evaluating the nets on it (episode.py:194-212,
  * net.py:64-85 run on all of [T, B]) and masks the results (`valid`, rnad.py:369).  The *_rows variants evaluate only the

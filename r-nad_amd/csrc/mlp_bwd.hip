@@ -440,6 +440,21 @@ extern "C" int64_t rnad_mlp_backward_workspace(int64_t N, int A, int W) {
     return bytes;
 }
 
+// The launch that N rows get on this device (host code only: what rnad_mlp_backward / _rows / _fold would launch).
+// out: waves per block | hidden-tile groups (grid y) | persistent blocks (grid x = partial rows of the reduction) | 1 = mlp_bwd_t.hip.
+extern "C" int rnad_mlp_backward_plan(int64_t N, int A, int W, int fold, int32_t *out) {
+    RNAD_REQUIRE(out, "rnad_mlp_backward_plan: null argument");
+    RNAD_REQUIRE(N >= 1 && A >= (fold ? 2 : 1) && A <= RNAD_MAX_ACTIONS && W >= kTile && W % kTile == 0,
+                 "rnad_mlp_backward_plan: no backward for N=%lld, A=%d, width=%d, fold=%d", (long long)N, A, W, fold);
+    BwdPlan p;
+    RNAD_REQUIRE(mlp_backward_plan(N, W, A, &p, fold != 0), "rnad_mlp_backward_plan: weights do not fit the LDS (A=%d, width=%d)", A, W);
+    out[0] = p.waves;
+    out[1] = p.groups;
+    out[2] = p.grid_x;
+    out[3] = p.resident ? 1 : 0;
+    return 0;
+}
+
 static int mlp_backward_launch(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int W, const float *packed, const void *obs,
                                int obs_half, const float *dlogits, const float *dvalue, float *g_vw0, float *g_vb0, float *g_vw1,
                                float *g_vb1, float *g_pw0, float *g_pb0, float *g_pw1, float *g_pb1, float *workspace, void *stream_,

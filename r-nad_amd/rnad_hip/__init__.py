@@ -509,18 +509,31 @@ def mlp_backward_supported(A, W):
     return W % 32 == 0 and lib().rnad_mlp_backward_workspace(C.c_int64(32), A, W) > 0
 
 
-def mlp_backward(packed, weights, obs, A, dlogits, dvalue, live=None, out=None, fold=False, capacity=None):
+def mlp_backward_plan(N, A, W, fold=False):
+    """The launch mlp_backward gives N rows on the current device (rnad_mlp_backward_plan): waves per workgroup, groups of hidden tiles,
+    grid_x (persistent workgroups = partial rows of the reduction), resident (the register-resident kernel)."""
+    import types
+
+    out = (C.c_int32 * 4)()
+    _check(lib().rnad_mlp_backward_plan(C.c_int64(N), A, W, int(bool(fold)), out))
+    return types.SimpleNamespace(waves=out[0], groups=out[1], grid_x=out[2], resident=bool(out[3]))
+
+
+def mlp_backward(packed, weights, obs, A, dlogits, dvalue, live=None, out=None, fold=False, capacity=None, workspace=None):
     """Gradients of the 8 Linear tensors (MLP_KEYS order) for dL/dlogits [N, A], dL/dvalue [N(,1)].
     live: a LiveRows -- only those rows contribute (the caller guarantees the others carry zero gradients).
     out: eight preallocated tensors shaped like the weights (e.g. views of one flat all-reduce bucket) to write into.
-    fold: False, or the TreeHandle whose observation table `obs` is (as mlp_forward)."""
+    fold: False, or the TreeHandle whose observation table `obs` is (as mlp_forward).
+    workspace: a preallocated fp32 tensor of at least rnad_mlp_backward_workspace(N, A, W) bytes for the per-workgroup partials."""
     fold = _fold_checked(fold, obs, "mlp_backward")
     N = obs.numel() // (2 * A * A)
     W = weights[0].shape[0]
     half = obs.dtype == F16
     grads = [torch.empty_like(w) for w in weights] if out is None else list(out)
     assert len(grads) == len(weights) and all(g.shape == w.shape for g, w in zip(grads, weights))
-    ws = torch.empty((lib().rnad_mlp_backward_workspace(C.c_int64(N), A, W) // 4,), dtype=F32, device=obs.device)
+    ws_floats = lib().rnad_mlp_backward_workspace(C.c_int64(N), A, W) // 4
+    ws = torch.empty((ws_floats,), dtype=F32, device=obs.device) if workspace is None else workspace
+    assert ws.numel() >= ws_floats, "workspace smaller than rnad_mlp_backward_workspace(N, A, W)"
     common = (A, W, _dp(packed, F32, "packed"), _dp(obs, F16 if half else F32, "obs"), int(half), _dp(dlogits, F32, "dlogits"),
               _dp(dvalue, F32, "dvalue"), *[_dp(g, F32, "grad") for g in grads], _dp(ws, F32, "workspace"), _stream())
     if fold:  # (packed: the fold image; gradients of the eight original tensors)
