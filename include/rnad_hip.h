@@ -733,8 +733,27 @@ int rnad_optimizer_step(int n_tensors, const int64_t *sizes, float *const *param
                         float *const *exp_avg_sq, float *const *step, float *const *target, const rnad_adam_params_t *hp,
                         float *total_norm, int mlp_A, int mlp_W, int mlp_fold, float *packed_param, float *packed_target, rnad_step_queue_t *advance,
                         uint32_t *ticket, void *stream);
+/* The same tail, in one launch, for the 8 + 8 depth tensors of a fused ConvNet (rnad_conv_supported shapes; anything else and a null
+ * required argument return non-zero with a message).  param / exp_avg / exp_avg_sq / step / target: HOST arrays of 8 + 8 depth device
+ * pointers in net.parameters() order -- the order of rnad_conv_pack and of the flat bucket `grads` rnad_conv_backward writes (read only
+ * here); target may be NULL: no EMA.  The arithmetic, the summation order of the norm, total_norm, advance and ticket are
+ * rnad_optimizer_step's (one copy of the code): the same bucket and state give the same bits whether they are handed over as 8 + 8 depth
+ * tensors here or as one tensor there.  Every step counter advances once.
+ * packed_param / packed_target (either may be NULL; packed_target needs target): images of rnad_conv_pack's layout.  Every new weight / new
+ * target weight is ALSO written into each image slot rnad_conv_pack would fill from it -- a conv weight W[o, c, t] into A - |t - (A - 1)|
+ * entries of the forward Toeplitz operand and, in the tower layers, as many of the transposed one; a conv bias into the slot of
+ * row_conv.bias[o] + col_conv.bias[o] (the sum of the NEW values, taken by the one thread that updates both); a head weight or bias into its
+ * one slot.  Padding slots (the pre-layer's K rounded up to a multiple of 4, the image's tail) are never written: they keep the zeros of
+ * the pack that initialised the image.  So a step carries no pack launch.
+ * rnad_conv_image_slots (host only, no GPU): the image slots of `element` of tensor `tensor` (net.parameters() order) -- the map the
+ * kernel scatters by.  Writes up to `capacity` slot indices and returns their number (at most 2 A), -1 with a message for an unsupported
+ * shape or an element that does not exist.  The two biases of a channel name the same slot. */
+int rnad_conv_optimizer_step(int A, int Ch, int depth, float *const *param, float *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                             float *const *step, float *const *target, const rnad_adam_params_t *hp, float *total_norm, float *packed_param,
+                             float *packed_target, rnad_step_queue_t *advance, uint32_t *ticket, void *stream);
+int rnad_conv_image_slots(int A, int Ch, int depth, int tensor, int64_t element, int32_t *slots, int capacity);
 /* ------------------------------------------------------------------------------------------------
- * NashConv  --  util/metric.py:93-175 (NashConvData.get_nashconv), level-batched on the GPU
+ * NashConv --  util/metric.py:93-175 (NashConvData.get_nashconv), level-batched on the GPU
  * instead of one Python frame per state.  joint_policy f32 [S,2A] (device) for every state below
  * `state_index`; root_policy f32 [2A] (device) is the row used AT state_index (the reference
  * recursion passes self.joint_policy to descendants, :148-151).  Outputs f32/int32 [S] (device):

@@ -26,6 +26,7 @@
 // order); one reduction kernel folds the Toeplitz diagonals and sums the workgroups in ascending order -- no float atomics, bitwise
 // reproducible.
 #include "common.hpp"
+#include "conv_shape.hpp"
 #include "rollout_math.hpp"
 
 #include <algorithm>
@@ -37,53 +38,9 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kConvThreads = 256, kConvWaves = kConvThreads / 64;
-constexpr int kConvMaxDepth = 8;
-constexpr int kConvMaxTensors = 4 * (2 * kConvMaxDepth + 1) + 4;
 constexpr int kConvBwdGrid = 256;   // workgroups of the backward launch = partial slices of the reduction
 constexpr int kConvFwdGrid = 1024;
 constexpr size_t kConvLds = 160 * 1024;
-
-// Sizes and offsets of one net shape: the packed image, a workgroup's partial slice and the flat parameter bucket.
-// Layer l: 0 = pre, 1 + 2 d = tower.d.conv0, 2 + 2 d = tower.d.conv1.
-struct ConvShape {
-    int A, Ch, D, L;
-    int F, P, XP;      // floats per sample of an activation, its LDS stride (odd), the LDS stride of an observation
-    int M, Mt, KS, KS0;  // outputs per product, their tiles, k-steps of a tower product and of the pre-layer's (K = 2 A, zero padded)
-    __host__ __device__ ConvShape(int A_, int Ch_, int D_) : A(A_), Ch(Ch_), D(D_), L(2 * D_ + 1) {
-        F = Ch * A * A; P = F | 1; XP = (2 * A * A) | 1;
-        M = Ch * A; Mt = M / 16; KS = M / 4; KS0 = (2 * A + 3) / 4;
-    }
-    __host__ __device__ int cin(int l) const { return l ? Ch : 2; }
-    __host__ __device__ int ks(int l) const { return l ? KS : KS0; }
-    __host__ __device__ int image(int l) const { return Mt * ks(l) * 64; }  // one Toeplitz operand image
-    // packed: per layer [row image][column image][bias br + bc], then the transposed images of the tower layers, then the heads
-    __host__ __device__ int fwd(int l) const { return l == 0 ? 0 : (2 * Mt * KS0 * 64 + Ch) + (l - 1) * (2 * Mt * KS * 64 + Ch); }
-    __host__ __device__ int bias(int l) const { return fwd(l) + 2 * image(l); }
-    __host__ __device__ int tr(int l) const { return fwd(L) + (l - 1) * 2 * Mt * KS * 64; }  // l >= 1
-    __host__ __device__ int wp() const { return tr(L); }
-    __host__ __device__ int wv() const { return wp() + A * F; }
-    __host__ __device__ int bp() const { return wv() + F; }
-    __host__ __device__ int bv() const { return bp() + A; }
-    __host__ __device__ int packed_total() const { return (bv() + 1 + 3) & ~3; }
-    // a workgroup's partials: per layer [gTrow M x Cin A][gTcol M x Cin A][bias Ch], then gWp [A, F], gWv [F], gbp [A], gbv
-    __host__ __device__ int ncols(int l) const { return cin(l) * A; }
-    __host__ __device__ int part(int l) const { return l == 0 ? 0 : (2 * M * 2 * A + Ch) + (l - 1) * (2 * M * M + Ch); }
-    __host__ __device__ int part_bias(int l) const { return part(l) + 2 * M * ncols(l); }
-    __host__ __device__ int part_wp() const { return part(L); }
-    __host__ __device__ int part_wv() const { return part_wp() + A * F; }
-    __host__ __device__ int part_bp() const { return part_wv() + F; }
-    __host__ __device__ int part_bv() const { return part_bp() + A; }
-    __host__ __device__ int part_total() const { return part_bv() + 1; }
-    // the flat bucket, net.parameters() order
-    __host__ __device__ int wsize(int l) const { return Ch * cin(l) * (2 * A - 1); }
-    __host__ __device__ int n_params() const { return 2 * (wsize(0) + Ch) + 2 * D * 2 * (wsize(1) + Ch) + A * F + A + F + 1; }
-    __host__ __device__ size_t fwd_lds(int NT) const { return (size_t)3 * NT * 16 * P * sizeof(float); }
-    // backward: H[0..D], T[0..D-1], R[0..D-2] (the last block's R lives in Gz), G, Gz, U, the observations and dL/dlogits | dL/dv
-    __host__ __device__ size_t bwd_lds() const { return (size_t)16 * ((3 * D + 3) * P + XP + A + 1) * sizeof(float); }
-    // backward, LEAN (shapes whose saved activations do not fit, e.g. A = 5, Ch = 16, D = 2): H[0..D-1], one T, G, Gz, U -- H_D lives in Gz
-    // until the heads are done, relu(conv0) and relu(conv1) of a block are recomputed when the walk back reaches it
-    __host__ __device__ size_t bwd_lds_lean() const { return (size_t)16 * ((D + 4) * P + XP + A + 1) * sizeof(float); }
-};
 
 __device__ __forceinline__ int board_index(int A, int dir, int ch, int b, int x) { return dir == 0 ? (ch * A + b) * A + x : (ch * A + x) * A + b; }
 

@@ -158,7 +158,10 @@ class RNaD:
         # A ConvNet takes this step only when asked (True); None keeps its all-rows step.
         self.lazy_rows = None
         self.last_rows = None  # rnad_hip.LiveRows of the last lazy step
-        self.fused_optimizer = True  # clip + Adam + EMA target of the MLP in one launch (csrc/optim.hip) instead of ~8 torch launches
+        # clip + Adam + EMA target in one launch that also keeps the packed weight images current (csrc/optim.hip) instead of ~8 torch
+        # launches and the pack launches of the next step.  None: the net family's own default (FUSED_TAIL_AUTO: on for an MLP, off for a
+        # ConvNet, whose tail is opt-in); True / False force it.
+        self.fused_optimizer = None
         # Data parallel, per-row mode: what a rank does on the 2S rows of the tree (table forwards + records, backward) does not shrink
         # with its share of the batch.  shard_rows = True also shards THAT: rank r evaluates rows [r * 2S / N, (r + 1) * 2S / N), the
         # record tables are all-gathered, the learner's 64-bit per-row sums are all-reduced (exact: every rank then holds the sums of
@@ -458,7 +461,8 @@ class RNaD:
 
     def _row_extras(self):
         """The net's family also has the extras of the per-row step: the legal fold, row sharding, the fused records launch
-        (rnad_mlp_rows_records) and the one-launch optimiser tail.  Today: the MLP.  (Lazy rows are asked for separately: _lazy_rows_ready.)"""
+        (rnad_mlp_rows_records).  Today: the MLP.  (Lazy rows and the optimiser tail are asked for separately: _lazy_rows_ready,
+        _fused_optimizer_on.)"""
         return bool(getattr(self.net, "ROW_EXTRAS", False))
 
     def _lazy_rows_ready(self):
@@ -469,6 +473,13 @@ class RNaD:
 
     def _fused_mlp(self):
         return self._fused_net() and self._row_extras()
+
+    def _fused_optimizer_on(self):
+        """RNaD.fused_optimizer resolved: None is the default of the net's family (nn/net.py FUSED_TAIL_AUTO)."""
+        want = getattr(self, "fused_optimizer", None)
+        if want is None:
+            return bool(getattr(self.net, "FUSED_TAIL_AUTO", False))
+        return bool(want)
 
     def _tabular_mode(self, T, B):
         """RNaD.tabular if the tree is small enough next to a [T, B] trajectory for the table evaluation to pay, else False."""
@@ -1187,10 +1198,13 @@ class RNaD:
             torch._foreach_add_(tgt, src, alpha=self.gamma_averaging)
 
     def _fused_tail(self):
-        """rnad_hip.OptimizerStep over the learner's eight tensors (clip + Adam + EMA in one launch), or None when the plain torch
-        sequence must run: another net type, a CPU run, an optimiser that is not the reference's Adam (rnad.py:232-237), or Adam
-        state that does not exist yet (torch creates it in its first step())."""
-        if not getattr(self, "fused_optimizer", True) or not self._fused_mlp() or not isinstance(self.net_target, net.MLP):
+        """The net family's one-launch tail over the learner's tensors (nn/net.py optimizer_tail: clip + Adam + EMA, the packed images
+        kept current), or None when the plain torch sequence must run: switched off (_fused_optimizer_on), a net without fused kernels or
+        without such a tail, a CPU run, an optimiser that is not the reference's Adam (rnad.py:232-237), or Adam state that does not
+        exist yet (torch creates it in its first step())."""
+        if not self._fused_optimizer_on() or not self._fused_net() or getattr(self.net, "optimizer_tail", None) is None:
+            return None
+        if type(self.net_target) is not type(self.net):
             return None
         opt = self.optimizer
         if type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1:
@@ -1215,9 +1229,8 @@ class RNaD:
         lr = grp["lr"]
         if torch.is_tensor(lr):
             return None
-        tail = rnad_hip.OptimizerStep(weights, [st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states], steps,
-                                      self.net_target._weights(), lr, grp["betas"][0], grp["betas"][1], grp["eps"], self.grad_clip,
-                                      self.gamma_averaging, packed=tuple(images), A=self.tree.max_actions, fold=fold)
+        tail = self.net.optimizer_tail(self.net_target, [st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states], steps,
+                                       (lr, grp["betas"][0], grp["betas"][1], grp["eps"], self.grad_clip, self.gamma_averaging), images, fold=fold)
         self._fused_tail_cache = (key, tail)
         self._packed_cache["maintained"] = fold
         return tail
@@ -1252,7 +1265,7 @@ class RNaD:
         return (id(buffer), id(self.net), id(self.net_target), id(self.net_reg), id(self.net_reg_), id(self.optimizer), id(self.tree.handle()), opt,
                 self.batch_size, self.tabular, getattr(self, "tabular_gate", 8), self.eta, self.beta, self.neurd_clip, self.grad_clip,
                 self.c_bar, self.roh_bar, self.vtrace_gamma, self.value_weight, self.neurd_weight, self.epsilon_threshold, self.n_discrete,
-                self.gamma_averaging, getattr(self, "obs_half", False), getattr(self, "store_actor_values", False), getattr(self, "fused_optimizer", True),
+                self.gamma_averaging, getattr(self, "obs_half", False), getattr(self, "store_actor_values", False), self._fused_optimizer_on(),
                 getattr(self, "compact_trajectory", True), getattr(self, "lazy_rows", None), rnad_hip.plan_knobs(), os.environ.get("RNAD_LEAF_CHUNK"),
                 getattr(self, "fold_legal", True), self._fuse_now(), self._fuse_now() and self._distinct_now(), getattr(self, "analytic_norm", True), os.environ.get("RNAD_FUSED_DISTINCT"), os.environ.get("RNAD_FUSED_CHUNK"),
                 getattr(self, "leaf_paths", None), os.environ.get("RNAD_LEAF_PATHS"), os.environ.get("RNAD_LEAF_CROWDED_LANES"))

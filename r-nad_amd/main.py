@@ -2,7 +2,7 @@
 R-NaD for a few values of eta on the MI355X.  Lives next to the `environment / learn / nn / util` packages, exactly like the
 reference's script lives next to its own, and uses only their reference-compatible API.
 
-    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log] [--net convnet --channels 16 --depth 2 [--lazy-rows]]
+    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log] [--net convnet --channels 16 --depth 2 [--lazy-rows] [--fused-tail]]
 """
 import argparse
 import logging
@@ -27,6 +27,9 @@ if __name__ == "__main__":
     ap.add_argument("--depth", type=int, default=2, help="ConvNet: residual blocks")
     ap.add_argument("--lazy-rows", action="store_true",
                     help="RNaD.lazy_rows = True: the nets run on the rows the batch stages and visits (a ConvNet's opt-in; automatic for the MLP)")
+    ap.add_argument("--fused-tail", action="store_true",
+                    help="RNaD.fused_optimizer = True: clip + Adam + EMA in one launch that keeps the packed images current (a ConvNet's opt-in; "
+                         "the MLP's default)")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
     if not torch.cuda.is_available():
@@ -71,5 +74,7 @@ if __name__ == "__main__":
         trial.compact_log = args.compact_log
         if args.lazy_rows:
             trial.lazy_rows = True
+        if args.fused_tail:
+            trial.fused_optimizer = True
         trial.run(log_mod=10, expl_mod=1, checkpoint_mod=args.steps)
         print(f"eta={eta}: NashConv by update:", [round(v, 3) for _, _, v in trial.nashconv_history])

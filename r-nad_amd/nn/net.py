@@ -18,7 +18,8 @@ non-fp32 weights, shapes rnad_conv_supported declines -- runs the plain torch mo
 
 Both classes expose the same small interface to learn/rnad.py and environment/episode.py (per_row_ready, pack_many, packed_size,
 tables_forward, table_forward, backward_rows, ROW_EXTRAS, ROLLOUT_KERNEL; for lazy rows: lazy_rows_ready, LAZY_ROWS_AUTO, staged_actor,
-ACTOR_WRITES_VALUE), so the trainer asks the net instead of knowing its family.
+ACTOR_WRITES_VALUE; for the one-launch optimiser tail: optimizer_tail, FUSED_TAIL_AUTO), so the trainer asks the net instead of knowing
+its family.
 """
 import torch
 import torch.nn as nn
@@ -45,6 +46,13 @@ class MLP(nn.Module):
     ROLLOUT_KERNEL = True  # rnad_rollout_run evaluates this net inside the native rollout loop
     LAZY_ROWS_AUTO = True  # RNaD.lazy_rows = None: lazy rows whenever the tree has more rows than the rank plays lanes
     ACTOR_WRITES_VALUE = False  # separate heads: the staged actor is the policy head alone, the value head runs on the visited rows later
+    FUSED_TAIL_AUTO = True  # RNaD.fused_optimizer = None: the one-launch optimiser tail whenever it applies
+
+    def optimizer_tail(self, target, exp_avg, exp_avg_sq, steps, hp, images, fold=False):
+        """Clip + Adam + EMA of this net (EMA target: `target`, a net of the same shape) in one launch that also keeps `images` = (this
+        net's packed image, the target's) current: rnad_optimizer_step.  hp = (lr, beta1, beta2, eps, max_norm, ema)."""
+        return rnad_hip.OptimizerStep(self._weights(), exp_avg, exp_avg_sq, steps, target._weights(), *hp, packed=tuple(images),
+                                      A=self.max_actions, fold=fold)
 
     def per_row_ready(self):
         """The fused forward AND backward cover this net: RNaD's per-row step (and its hand-written backward) applies."""
@@ -233,10 +241,11 @@ class ConvNet(nn.Module):
     """Two-headed CrossConv tower: pre (CrossConv 2 -> channels, no relu), `depth` ConvResBlocks, then a policy and a value Linear on
     the activation flattened in (c, i, j) order.  State-dict keys (pre.*, tower.<d>.*, policy.*, value.*) are the reference's."""
 
-    ROW_EXTRAS = False      # no legal fold, row sharding, fused records launch or fused optimiser tail for this family
+    ROW_EXTRAS = False      # no legal fold, row sharding or fused records launch for this family
     ROLLOUT_KERNEL = False  # the native rollout loop evaluates MLPs only: a ConvNet actor is a table, or is called per step
     LAZY_ROWS_AUTO = False  # lazy rows are opt-in for this family (RNaD.lazy_rows = True): None keeps the all-rows step
     ACTOR_WRITES_VALUE = True  # one tower under both heads: the staged actor launches leave the learner's value on every row they evaluate
+    FUSED_TAIL_AUTO = False  # the one-launch optimiser tail is opt-in for this family (RNaD.fused_optimizer = True): None keeps torch's
 
     def __init__(self, max_actions, channels, depth=1, batch_norm=True, device=torch.device("cpu:0"), dtype=torch.float):
         super().__init__()
@@ -288,6 +297,13 @@ class ConvNet(nn.Module):
                 rnad_hip.conv_forward_actor(handle, packed, *shape, table, logit, v, policy_rows, rows=rows)
 
         return staged_actor
+
+    def optimizer_tail(self, target, exp_avg, exp_avg_sq, steps, hp, images, fold=False):
+        """MLP.optimizer_tail for this family: rnad_conv_optimizer_step over the 8 + 8 depth tensors, every new weight also written
+        into its Toeplitz slots of the two packed images."""
+        assert not fold
+        return rnad_hip.ConvOptimizerStep(self._shape(), self._weights(), exp_avg, exp_avg_sq, steps, target._weights(), *hp,
+                                          packed=tuple(images))
 
     def packed_size(self, fold=False):
         assert not fold

@@ -1797,14 +1797,67 @@ class OptimizerStep:
         # the kernel's workgroups count themselves here (and the last one resets it): this optimiser's own word, not a device global
         self.ticket = torch.zeros((1,), dtype=I32, device=params[0].device)
 
-    def __call__(self, flat, advance=None):
-        """advance: a step queue (step_queue_set) to move on once the step is over."""
+    def __call__(self, flat, advance=None, total_norm=None):
+        """advance: a step queue (step_queue_set) to move on once the step is over.  total_norm: a device float for the bucket's 2-norm."""
         assert flat.numel() == self.numel and (advance is None or advance.numel() >= STEP_QUEUE_WORDS)
         img = self.packed or (None, None)
         _check(lib().rnad_optimizer_step(self.n, self.sizes, self.param, _dp(flat, F32, "grads"), self.m, self.v, self.step, self.target,
-                                         C.byref(self.hp), None, self.A, self.W, self.fold, _dp(img[0], F32, "packed_param", True),
+                                         C.byref(self.hp), _dp(total_norm, F32, "total_norm", True), self.A, self.W, self.fold, _dp(img[0], F32, "packed_param", True),
                                          _dp(img[1], F32, "packed_target", True), _dp(advance, torch.int64, "advance", True),
                                          _dp(self.ticket, I32, "ticket"), _stream()))
+
+
+def conv_image_slots(A, Ch, depth, tensor, element):
+    """The slots of the packed ConvNet image (conv_pack) that hold element `element` of tensor `tensor` (net.parameters() order):
+    rnad_conv_image_slots, the map ConvOptimizerStep scatters by.  Host only -- no GPU.  The row and the column bias of a channel name the
+    same slot (it holds their sum)."""
+    buf = (C.c_int32 * (2 * MAX_ACTIONS))()
+    n = int(lib().rnad_conv_image_slots(A, Ch, depth, int(tensor), int(element), buf, len(buf)))
+    if n < 0:
+        _check(1)
+    assert n <= len(buf)
+    return list(buf[:n])
+
+
+class ConvOptimizerStep:
+    """rnad_conv_optimizer_step bound to fixed tensors: OptimizerStep for the 8 + 8 depth tensors of a fused ConvNet (net.parameters()
+    order, gradients back to back in one flat bucket in that order).  The pointer arrays are built once."""
+
+    def __init__(self, shape, params, exp_avg, exp_avg_sq, steps, targets, lr, beta1, beta2, eps, max_norm, ema, packed=None):
+        """shape = (A, Ch, depth).  packed = (image of params, image of targets), either may be None: conv_pack images the kernel keeps
+        current -- every new weight also goes into each of its image slots, so a step needs no pack launch."""
+        A, Ch, depth = (int(x) for x in shape)
+        n = 8 + 8 * depth
+        if not conv_supported(A, Ch, depth):
+            raise RnadHipError(f"ConvOptimizerStep: unsupported shape (A={A}, channels={Ch}, depth={depth})")
+        assert len(params) == len(exp_avg) == len(exp_avg_sq) == len(steps) == n and (targets is None or len(targets) == n)
+        self.shape, self.n = (A, Ch, depth), n
+        self.numel = conv_param_count(A, Ch, depth)
+        taps = 2 * A - 1
+        sizes = ([Ch * 2 * taps, Ch] * 2 + [Ch * Ch * taps, Ch] * (4 * depth) + [A * Ch * A * A, A, Ch * A * A, 1])
+        groups = [params, exp_avg, exp_avg_sq] + ([targets] if targets is not None else [])
+        assert all(t.numel() == size for ts in groups for t, size in zip(ts, sizes)), "ConvOptimizerStep: tensors of another shape"
+        assert all(s.numel() == 1 for s in steps)
+        packed = tuple(packed) if packed is not None else (None, None)
+        size = int(lib().rnad_conv_packed_size(A, Ch, depth))
+        assert all(img is None or img.numel() == size for img in packed)
+        assert packed[1] is None or targets is not None, "a packed target image needs the target tensors"
+        self.packed = packed
+        self._keep = (params, exp_avg, exp_avg_sq, steps, targets, packed)
+        arr = lambda ts, name: (C.c_void_p * n)(*[_dp(t.detach(), F32, name).value for t in ts])  # noqa: E731
+        self.param, self.m, self.v, self.step = arr(params, "param"), arr(exp_avg, "exp_avg"), arr(exp_avg_sq, "exp_avg_sq"), arr(steps, "step")
+        self.target = arr(targets, "target") if targets is not None else None
+        self.hp = AdamParams(float(lr), float(beta1), float(beta2), float(eps), float(max_norm), float(ema))
+        # the kernel's workgroups count themselves here (and the last one resets it): this optimiser's own word, not a device global
+        self.ticket = torch.zeros((1,), dtype=I32, device=params[0].device)
+
+    def __call__(self, flat, advance=None, total_norm=None):
+        """advance: a step queue (step_queue_set) to move on once the step is over.  total_norm: a device float for the bucket's 2-norm."""
+        assert flat.numel() == self.numel and (advance is None or advance.numel() >= STEP_QUEUE_WORDS)
+        _check(lib().rnad_conv_optimizer_step(*self.shape, self.param, _dp(flat, F32, "grads"), self.m, self.v, self.step, self.target,
+                                              C.byref(self.hp), _dp(total_norm, F32, "total_norm", True),
+                                              _dp(self.packed[0], F32, "packed_param", True), _dp(self.packed[1], F32, "packed_target", True),
+                                              _dp(advance, torch.int64, "advance", True), _dp(self.ticket, I32, "ticket"), _stream()))
 
 
 def make_learn_params(alpha, eta, lambda_=1.0, c=1.0, rho=1.0, gamma=1.0, clip=1e3, threshold=2.0, w_v=1.0, w_n=1.0,

@@ -12,6 +12,10 @@
 all-rows step) and on (staged actor, target and backward on the visited rows), on the pruned 5x5, 4-outcome configs[3]-shaped tree and on
 the configs[1] tree, with the rows each step ran on.  The two trainers of a tree start from the same seed; their windows alternate.
 
+--tail runs a third leg instead (default --out profiles/convnet_tail.md): one default ConvNet train_step with the one-launch optimiser tail
+(RNaD.fused_optimizer = True: rnad_conv_optimizer_step, which also keeps the packed images current) off and on -- on the configs[1] tree, and
+with lazy rows on the configs[3]-shaped A = 5 tree of --lazy -- each with the kernel launches of one step.
+
 Times are device events around `reps` back-to-back calls after a warm-up of the same shapes; fused and torch windows alternate.  Needs the GPU: there is no CPU path.
 """
 import argparse
@@ -130,6 +134,86 @@ def lazy_leg(args, dev):
     print(text)
 
 
+def launches_of(step):
+    """Device kernels of one EAGER call of `step`, counted by torch's profiler (None where it cannot trace the device)."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            step()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA"))
+        return n or None
+    except Exception as err:  # the count is a by-product of the leg
+        print(f"launch count not taken: {err}", flush=True)
+        return None
+
+
+def tail_leg(args, dev):
+    """One default ConvNet train_step with the one-launch optimiser tail off and on, per tree: ms per step (mean and spread over
+    alternating windows) and the kernel launches of one eager step."""
+    os.environ["RNAD_SAVE_DIR"] = tempfile.mkdtemp(prefix="rnad_conv_tail_")
+    B = 1 << args.lanes_log2
+    out = args.out or os.path.join(ROOT, "profiles", "convnet_tail.md")
+    lines = [f"# ConvNet train_step with the one-launch optimiser tail off / on, channels = {args.channels}, depth = {args.depth}, 2^{args.lanes_log2} lanes", "",
+             f"Build {rnad_hip.source_hash()}.  Device events around back-to-back steps; every window lasts about {WINDOW_MS / 1000:g} s after 8 priming steps of "
+             f"its trainer (eager warm-up and the graph capture); the windows of the two trainers alternate, {args.rounds} rounds; a figure is the mean over "
+             "the rounds, with the smallest and the largest round beside it.  Launches: device kernels of one eager step of the same trainer after the "
+             "timed windows, counted by torch's profiler.", "",
+             "| tree | lazy_rows | fused tail | ms per step (min .. max) | launches per eager step | tail in use | hipGraph replay |",
+             "|---|---|---|---|---|---|---|"]
+    trees = (("configs[1]: 3x3, depth 6", dict(max_actions=3, max_transitions=1, depth_bound=6, transition_threshold=0.0), (0, 0), None),
+             ("configs[3] shape: 5x5, 4 outcomes, depth 8, threshold 0.1, pruned 7/8",
+              dict(max_actions=5, max_transitions=4, depth_bound=8, transition_threshold=0.1), (7, 8), True))
+    ratios = []
+    for what, kw, prune, lazy in trees:
+        tree = Tree(device=dev, **kw)
+        tree.generate_native(seed=0, prune=prune)
+        A = tree.max_actions
+        legs = {}
+        for fused in (False, True):
+            torch.manual_seed(0)
+            rn = RNaD(tree=tree, device=dev, directory_name=f"tail_{A}_{fused}", batch_size=B, eta=0.2, b1_adam=0.0, lr=5e-5,
+                      net_params={"type": "ConvNet", "max_actions": A, "channels": args.channels, "depth": args.depth, "batch_norm": False})
+            rn.initialize()
+            rn.lazy_rows, rn.fused_optimizer = lazy, fused
+            buf = Buffer(1)
+
+            def step(rn=rn, buf=buf):
+                rn.train_step(buf, alpha=0.5)
+                rn.total_steps += 1
+
+            for _ in range(8):
+                step()
+            torch.cuda.synchronize()
+            legs[fused] = (rn, step, [])
+        for _ in range(args.rounds):
+            for fused in (False, True):
+                legs[fused][2].append(timeit(legs[fused][1], args.steps))
+        for fused in (False, True):
+            rn, step, ms = legs[fused]
+            replay = bool(getattr(rn, "_graph", None) and rn._graph.get("graph") is not None)
+            in_use = rn._fused_tail() is not None
+            rn.use_graph = False  # (one eager step, for the launch count)
+            launches = launches_of(step)
+            mean = sum(ms) / len(ms)
+            lines.append(f"| {what} | {'on' if lazy else 'off'} | {'on' if fused else 'off'} | {mean:.3f} ({min(ms):.3f} .. {max(ms):.3f}) | "
+                         f"{'not counted' if launches is None else launches} | {in_use} | {replay} |")
+            print(lines[-1], flush=True)
+        off, on = (sum(legs[k][2]) / len(legs[k][2]) for k in (False, True))
+        ratios.append(f"- {what}: tail off / tail on = {off / on:.3f}x ({off:.3f} ms / {on:.3f} ms).")
+        legs.clear()
+        del tree
+        torch.cuda.empty_cache()
+    lines += ["", "Tail off is the step of the same build with RNaD.fused_optimizer unset (rnad_clip_grad_norm, torch's fused Adam, two _foreach EMA "
+              "launches and two rnad_conv_pack launches on the next step); the ratio against it:", ""] + ratios
+    text = "\n".join(lines) + "\n"
+    with open(out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", type=int, default=16)
@@ -142,11 +226,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-torch", action="store_true", help="leave the torch-module baseline out")
     ap.add_argument("--lazy", action="store_true", help="only the lazy-rows leg: a ConvNet train_step with lazy_rows off and on, on two trees")
+    ap.add_argument("--tail", action="store_true", help="only the optimiser-tail leg: a ConvNet train_step with RNaD.fused_optimizer off and on, on two trees")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "conv_bench needs the MI355X"
     dev = torch.device("cuda:0")
     if args.lazy:
         return lazy_leg(args, dev)
+    if args.tail:
+        return tail_leg(args, dev)
     torch.manual_seed(0)
     A = 3
     tree = Tree(device=dev, max_actions=A, max_transitions=1, depth_bound=6, transition_threshold=0.0)
