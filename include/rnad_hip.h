@@ -140,7 +140,7 @@ int rnad_mlp_backward_rows(int64_t max_rows, const int32_t *rows, const int64_t 
 /* ------------------------------------------------------------------------------------------------
  * Fused ConvNet  --  nn/net.py:88-269 with batch_norm=False: h = pre(obs) (a CrossConv, no relu), D residual blocks
  * h += relu(conv1(relu(conv0(h)))), logits = policy(flatten h), value = value(flatten h).  Each CrossConv runs as two fp32-MFMA
- * products with Toeplitz-expanded weights (csrc/conv_tower.hip); fp32 observations only.
+ * products with Toeplitz-expanded weights (csrc/conv_tower.hip).  Observations are fp32, or -- the *_obs entry points -- fp16.
  *
  * weights: HOST array of 8 + 8 D device pointers in net.parameters() order (per CrossConv: row_conv.weight [Ch,Cin,1,2A-1],
  * row_conv.bias, col_conv.weight [Ch,Cin,2A-1,1], col_conv.bias; then policy.weight [A, Ch A^2], policy.bias, value.weight, value.bias).
@@ -171,6 +171,19 @@ int rnad_conv_backward(int64_t N, const int32_t *rows, const int64_t *n_rows, in
  * rows that are not listed are neither read nor written in any output. */
 int rnad_conv_forward_actor(const rnad_tree_t *tree, const int32_t *rows, const int64_t *n_rows, int Ch, int depth, const float *packed,
                             const float *obs, float *logits, float *value, float *policy_rows, void *stream);
+/* fp16 observation tables: rnad_conv_forward / rnad_conv_forward_actor / rnad_conv_backward with the MLP entry points' `const void *obs,
+ * int obs_half` in place of `const float *obs` -- obs_half = 0: fp32 [N, 2 A^2]; obs_half = 1: fp16 of the same shape (what an fp16
+ * trajectory buffer or rnad_observe with obs_half holds).  An fp16 element is converted to fp32 exactly (subnormals included) as the tile
+ * is loaded; the activations, the arithmetic and every output stay fp32, so an fp16 table gives the bits the fp32 entry point gives on the
+ * up-converted table, and no fp32 copy of the table exists anywhere.  A row is 4 A^2 bytes and the kernels read it as pairs of fp16
+ * values: an fp16 obs must be 4-byte aligned (refused otherwise).  Every other argument is its twin's; the three functions above are these with obs_half = 0. */
+int rnad_conv_forward_obs(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                          const void *obs, int obs_half, float *logits, float *value, void *stream);
+int rnad_conv_forward_actor_obs(const rnad_tree_t *tree, const int32_t *rows, const int64_t *n_rows, int Ch, int depth, const float *packed,
+                                const void *obs, int obs_half, float *logits, float *value, float *policy_rows, void *stream);
+int rnad_conv_backward_obs(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                           const void *obs, int obs_half, const float *dlogits, const float *dvalue, float *grads, float *workspace,
+                           void *stream);
 
 /* The legal fold.  An observation is [expected value A x A | legal mask A x A] (episode.py:62-68); on a tree whose states all have the
  * full A x A action set -- every configuration of BASELINE.json -- the legal plane is all ones in every row except the two rows of

@@ -30,6 +30,7 @@
 #include "rollout_math.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 using namespace rnad;
 
@@ -41,6 +42,24 @@ constexpr int kConvThreads = 256, kConvWaves = kConvThreads / 64;
 constexpr int kConvBwdGrid = 256;   // workgroups of the backward launch = partial slices of the reduction
 constexpr int kConvFwdGrid = 1024;
 constexpr size_t kConvLds = 160 * 1024;
+
+// fp16 observation tables (ObsT = __half): the observations of the NS samples from `first` on, converted to the fp32 the tower computes
+// with, -> dst[s * stride + f]; zeros past sample N.  The table holds rounded values and v_cvt_f32_f16 is exact, subnormals included, so
+// the kernels on a half table give the bits of the float kernels on the up-converted table.  Read as __half2 pairs: a row is 4 A^2 bytes,
+// so in a 4-byte aligned table (the entry points check) every row starts on a pair.
+__device__ __forceinline__ void stage_half_obs(float *dst, int stride, int NS, int A, int64_t first, int64_t N, const int32_t *__restrict__ rows,
+                                               const __half *__restrict__ obs) {
+    const __half2 *__restrict__ obs2 = reinterpret_cast<const __half2 *>(obs);
+    const int O2 = A * A;
+    for (int idx = threadIdx.x; idx < NS * O2; idx += kConvThreads) {
+        const int s = idx / O2, f = idx % O2;
+        const int64_t sample = first + s;
+        float2 x = float2{0.0f, 0.0f};
+        if (sample < N) x = __half22float2(obs2[(rows ? (int64_t)rows[sample] : sample) * O2 + f]);
+        dst[s * stride + 2 * f] = x.x;
+        dst[s * stride + 2 * f + 1] = x.y;
+    }
+}
 
 __device__ __forceinline__ int board_index(int A, int dir, int ch, int b, int x) { return dir == 0 ? (ch * A + b) * A + x : (ch * A + x) * A + b; }
 
@@ -104,9 +123,9 @@ struct FwdActor {
     const uint8_t *__restrict__ mask_tab;   // [2S]
 };
 
-template <int NT, typename Epi>
+template <int NT, typename Epi, typename ObsT>
 __global__ __launch_bounds__(kConvThreads) void k_conv_forward(int64_t N, const int32_t *__restrict__ rows, const int64_t *__restrict__ n_rows,
-                                                               ConvShape sh, const float *__restrict__ packed, const float *__restrict__ obs,
+                                                               ConvShape sh, const float *__restrict__ packed, const ObsT *__restrict__ obs,
                                                                float *__restrict__ logits, float *__restrict__ value, Epi epi) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (n_rows) N = *n_rows < N ? *n_rows : N;  // the list never exceeds its capacity
@@ -115,12 +134,16 @@ __global__ __launch_bounds__(kConvThreads) void k_conv_forward(int64_t N, const 
     float *H = lds, *T = H + NS * P, *U = T + NS * P;
     const int64_t n_tiles = (N + NS - 1) / NS;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        for (int idx = threadIdx.x; idx < NS * OBS; idx += kConvThreads) {
-            const int s = idx / OBS, f = idx % OBS;
-            const int64_t sample = tile * NS + s;
-            float x = 0.0f;
-            if (sample < N) x = obs[(rows ? (int64_t)rows[sample] : sample) * OBS + f];
-            T[s * P + f] = x;
+        if constexpr (std::is_same<ObsT, __half>::value) {
+            stage_half_obs(T, P, NS, A, tile * NS, N, rows, obs);
+        } else {
+            for (int idx = threadIdx.x; idx < NS * OBS; idx += kConvThreads) {
+                const int s = idx / OBS, f = idx % OBS;
+                const int64_t sample = tile * NS + s;
+                float x = 0.0f;
+                if (sample < N) x = obs[(rows ? (int64_t)rows[sample] : sample) * OBS + f];
+                T[s * P + f] = x;
+            }
         }
         __syncthreads();
         cross_conv<NT>(sh, packed + sh.fwd(0), packed + sh.bias(0), sh.KS0, 2 * A, T, P, U, [&](int s, int f, float v) { H[s * P + f] = v; });
@@ -212,9 +235,9 @@ __device__ __forceinline__ void bias_grad(const ConvShape &sh, float *__restrict
     }
 }
 
-template <bool LEAN>
+template <bool LEAN, typename ObsT>
 __global__ __launch_bounds__(kConvThreads) void k_conv_backward(int64_t N, const int32_t *__restrict__ rows, const int64_t *__restrict__ n_rows,
-                                                                ConvShape sh, const float *__restrict__ packed, const float *__restrict__ obs,
+                                                                ConvShape sh, const float *__restrict__ packed, const ObsT *__restrict__ obs,
                                                                 const float *__restrict__ dlogits, const float *__restrict__ dvalue,
                                                                 float *__restrict__ workspace) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -232,10 +255,14 @@ __global__ __launch_bounds__(kConvThreads) void k_conv_backward(int64_t N, const
     const int64_t n_tiles = (N + NS - 1) / NS;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         // inputs of the tile; samples past the end carry zero gradients and so contribute nothing
-        for (int idx = threadIdx.x; idx < NS * OBS; idx += kConvThreads) {
-            const int s = idx / OBS, f = idx % OBS;
-            const int64_t sample = tile * NS + s;
-            X[s * XP + f] = sample < N ? obs[(rows ? (int64_t)rows[sample] : sample) * OBS + f] : 0.0f;
+        if constexpr (std::is_same<ObsT, __half>::value) {
+            stage_half_obs(X, XP, NS, A, tile * NS, N, rows, obs);
+        } else {
+            for (int idx = threadIdx.x; idx < NS * OBS; idx += kConvThreads) {
+                const int s = idx / OBS, f = idx % OBS;
+                const int64_t sample = tile * NS + s;
+                X[s * XP + f] = sample < N ? obs[(rows ? (int64_t)rows[sample] : sample) * OBS + f] : 0.0f;
+            }
         }
         for (int idx = threadIdx.x; idx < NS * A1; idx += kConvThreads) {
             const int s = idx / A1, a = idx % A1;
@@ -430,9 +457,9 @@ extern "C" int rnad_conv_pack(int A, int Ch, int depth, const float *const *weig
     return 0;
 }
 
-// One launch of k_conv_forward<NT, Epi> over N rows (or the row list), NT from fwd_tiles.
-template <typename Epi>
-static int conv_forward_launch(int64_t N, const int32_t *rows, const int64_t *n_rows, const ConvShape &sh, const float *packed, const float *obs,
+// One launch of k_conv_forward<NT, Epi, ObsT> over N rows (or the row list), NT from fwd_tiles.
+template <typename Epi, typename ObsT>
+static int conv_forward_launch(int64_t N, const int32_t *rows, const int64_t *n_rows, const ConvShape &sh, const float *packed, const ObsT *obs,
                                float *logits, float *value, Epi epi, void *stream) {
     if (N == 0) return 0;
     const int nt = fwd_tiles(sh);
@@ -441,7 +468,7 @@ static int conv_forward_launch(int64_t N, const int32_t *rows, const int64_t *n_
     const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, kConvFwdGrid);
 #define RNAD_CONV_FWD(NT_)                                                                                                                  \
     do {                                                                                                                                    \
-        auto kern = k_conv_forward<NT_, Epi>;                                                                                               \
+        auto kern = k_conv_forward<NT_, Epi, ObsT>;                                                                                         \
         if (lds > 64 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kConvThreads), lds, (hipStream_t)stream, N, rows, n_rows, sh, packed, obs, logits, value, \
                            epi);                                                                                                            \
@@ -454,31 +481,48 @@ static int conv_forward_launch(int64_t N, const int32_t *rows, const int64_t *n_
     return 0;
 }
 
-extern "C" int rnad_conv_forward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
-                                 const float *obs, float *logits, float *value, void *stream) {
+// obs_half: the observations are fp16 (rounded values, converted as a tile is staged: the arithmetic stays fp32), as in the MLP entry points.
+extern "C" int rnad_conv_forward_obs(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                                     const void *obs, int obs_half, float *logits, float *value, void *stream) {
     RNAD_REQUIRE(conv_shape_ok(A, Ch, depth), "rnad_conv_forward: unsupported shape (A=%d, channels=%d, depth=%d)", A, Ch, depth);
     RNAD_REQUIRE(packed && obs && (logits || value), "rnad_conv_forward: null argument");
     RNAD_REQUIRE(!rows == !n_rows, "rnad_conv_forward: rows and n_rows go together");
     RNAD_REQUIRE(N >= 0, "rnad_conv_forward: negative batch");
-    return conv_forward_launch(N, rows, n_rows, ConvShape(A, Ch, depth), packed, obs, logits, value, FwdPlain{}, stream);
+    RNAD_REQUIRE(!obs_half || ((uintptr_t)obs & 3) == 0, "rnad_conv_forward: an fp16 table must be 4-byte aligned");
+    const ConvShape sh(A, Ch, depth);
+    if (obs_half) return conv_forward_launch(N, rows, n_rows, sh, packed, (const __half *)obs, logits, value, FwdPlain{}, stream);
+    return conv_forward_launch(N, rows, n_rows, sh, packed, (const float *)obs, logits, value, FwdPlain{}, stream);
+}
+
+extern "C" int rnad_conv_forward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                                 const float *obs, float *logits, float *value, void *stream) {
+    return rnad_conv_forward_obs(N, rows, n_rows, A, Ch, depth, packed, obs, 0, logits, value, stream);
 }
 
 // A tabular ACTOR on (a row list of) the tree's 2S observations: rnad_conv_forward's logits and value (the same kernel, the same bits) and,
 // from its epilogue, the policy rows [2S, rnad_bucket_policy_row_stride(A)] the bucketed rollout kernels gather from.  rows / n_rows:
 // NULL = all 2S rows; rows that are not listed are neither read nor written.
-extern "C" int rnad_conv_forward_actor(const rnad_tree_t *tree, const int32_t *rows, const int64_t *n_rows, int Ch, int depth, const float *packed,
-                                       const float *obs, float *logits, float *value, float *policy_rows, void *stream) {
+extern "C" int rnad_conv_forward_actor_obs(const rnad_tree_t *tree, const int32_t *rows, const int64_t *n_rows, int Ch, int depth,
+                                           const float *packed, const void *obs, int obs_half, float *logits, float *value, float *policy_rows,
+                                           void *stream) {
     RNAD_REQUIRE(tree && packed && obs && logits && value && policy_rows, "rnad_conv_forward_actor: null argument");
     RNAD_REQUIRE(conv_shape_ok(tree->A, Ch, depth), "rnad_conv_forward_actor: unsupported shape (A=%d, channels=%d, depth=%d)", tree->A, Ch, depth);
     RNAD_REQUIRE(!rows == !n_rows, "rnad_conv_forward_actor: rows and n_rows go together");
     RNAD_REQUIRE(((uintptr_t)policy_rows & 15) == 0, "rnad_conv_forward_actor: policy_rows must be 16-byte aligned");
+    RNAD_REQUIRE(!obs_half || ((uintptr_t)obs & 3) == 0, "rnad_conv_forward_actor: an fp16 table must be 4-byte aligned");
     const ConvShape sh(tree->A, Ch, depth);
     RNAD_DISPATCH_A(tree->A, {
         FwdActor<kA> epi{policy_rows, tree->mask_tab};
-        const int rc = conv_forward_launch(2 * tree->S, rows, n_rows, sh, packed, obs, logits, value, epi, stream);
+        const int rc = obs_half ? conv_forward_launch(2 * tree->S, rows, n_rows, sh, packed, (const __half *)obs, logits, value, epi, stream)
+                                : conv_forward_launch(2 * tree->S, rows, n_rows, sh, packed, (const float *)obs, logits, value, epi, stream);
         if (rc) return rc;
     });
     return 0;
+}
+
+extern "C" int rnad_conv_forward_actor(const rnad_tree_t *tree, const int32_t *rows, const int64_t *n_rows, int Ch, int depth, const float *packed,
+                                       const float *obs, float *logits, float *value, float *policy_rows, void *stream) {
+    return rnad_conv_forward_actor_obs(tree, rows, n_rows, Ch, depth, packed, obs, 0, logits, value, policy_rows, stream);
 }
 
 static int conv_bwd_grid(int64_t N) { return (int)std::max<int64_t>(1, std::min<int64_t>((N + 15) / 16, kConvBwdGrid)); }
@@ -488,22 +532,47 @@ extern "C" int64_t rnad_conv_backward_workspace(int64_t N, int A, int Ch, int de
     return (int64_t)conv_bwd_grid(N) * ConvShape(A, Ch, depth).part_total() * (int64_t)sizeof(float);
 }
 
-extern "C" int rnad_conv_backward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
-                                  const float *obs, const float *dlogits, const float *dvalue, float *grads, float *workspace, void *stream) {
+// One launch of k_conv_backward<LEAN, ObsT> into the workgroups' slices of `workspace`.
+template <bool LEAN, typename ObsT>
+static int conv_backward_launch(int grid, size_t lds, hipStream_t s, int64_t N, const int32_t *rows, const int64_t *n_rows, const ConvShape &sh,
+                                const float *packed, const ObsT *obs, const float *dlogits, const float *dvalue, float *workspace) {
+    auto kern = k_conv_backward<LEAN, ObsT>;
+    if (lds > 64 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kConvThreads), lds, s, N, rows, n_rows, sh, packed, obs, dlogits, dvalue, workspace);
+    RNAD_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int rnad_conv_backward_obs(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                                      const void *obs, int obs_half, const float *dlogits, const float *dvalue, float *grads, float *workspace,
+                                      void *stream) {
     RNAD_REQUIRE(conv_shape_ok(A, Ch, depth), "rnad_conv_backward: unsupported shape (A=%d, channels=%d, depth=%d)", A, Ch, depth);
     RNAD_REQUIRE(packed && obs && dlogits && dvalue && grads && workspace, "rnad_conv_backward: null argument");
     RNAD_REQUIRE(!rows == !n_rows, "rnad_conv_backward: rows and n_rows go together");
     RNAD_REQUIRE(N >= 0, "rnad_conv_backward: negative batch");
+    RNAD_REQUIRE(!obs_half || ((uintptr_t)obs & 3) == 0, "rnad_conv_backward: an fp16 table must be 4-byte aligned");
     const ConvShape sh(A, Ch, depth);
     const bool lean = sh.bwd_lds() > kConvLds;  // the saved activations do not fit: recompute them per block
     const size_t lds = lean ? sh.bwd_lds_lean() : sh.bwd_lds();
     const int grid = conv_bwd_grid(N);
     hipStream_t s = (hipStream_t)stream;
-    auto kern = lean ? k_conv_backward<true> : k_conv_backward<false>;
-    if (lds > 64 * 1024) RNAD_HIP_OK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kConvThreads), lds, s, N, rows, n_rows, sh, packed, obs, dlogits, dvalue, workspace);
-    RNAD_HIP_OK(hipGetLastError());
+    int rc;
+    if (obs_half) {
+        const __half *o = (const __half *)obs;
+        rc = lean ? conv_backward_launch<true>(grid, lds, s, N, rows, n_rows, sh, packed, o, dlogits, dvalue, workspace)
+                  : conv_backward_launch<false>(grid, lds, s, N, rows, n_rows, sh, packed, o, dlogits, dvalue, workspace);
+    } else {
+        const float *o = (const float *)obs;
+        rc = lean ? conv_backward_launch<true>(grid, lds, s, N, rows, n_rows, sh, packed, o, dlogits, dvalue, workspace)
+                  : conv_backward_launch<false>(grid, lds, s, N, rows, n_rows, sh, packed, o, dlogits, dvalue, workspace);
+    }
+    if (rc) return rc;
     hipLaunchKernelGGL(k_conv_reduce, dim3((sh.n_params() + kConvThreads - 1) / kConvThreads), dim3(kConvThreads), 0, s, sh, grid, workspace, grads);
     RNAD_HIP_OK(hipGetLastError());
     return 0;
+}
+
+extern "C" int rnad_conv_backward(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int Ch, int depth, const float *packed,
+                                  const float *obs, const float *dlogits, const float *dvalue, float *grads, float *workspace, void *stream) {
+    return rnad_conv_backward_obs(N, rows, n_rows, A, Ch, depth, packed, obs, 0, dlogits, dvalue, grads, workspace, stream);
 }

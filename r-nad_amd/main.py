@@ -2,7 +2,7 @@
 R-NaD for a few values of eta on the MI355X.  Lives next to the `environment / learn / nn / util` packages, exactly like the
 reference's script lives next to its own, and uses only their reference-compatible API.
 
-    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log] [--net convnet --channels 16 --depth 2 [--lazy-rows] [--fused-tail]]
+    python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log] [--obs-half] [--net convnet --channels 16 --depth 2 [--lazy-rows] [--fused-tail]]
 """
 import argparse
 import logging
@@ -22,6 +22,8 @@ if __name__ == "__main__":
     ap.add_argument("--etas", type=float, nargs="*", default=[0, 0.2, 0.5, 1])
     ap.add_argument("--compact-log", action="store_true",
                     help="logged steps: statistics from per-row quantities and visit counts, one host sync (RNaD.compact_log)")
+    ap.add_argument("--obs-half", action="store_true",
+                    help="RNaD.obs_half = True: observations stored as fp16, arithmetic in fp32 (BASELINE.json configs[4]); either net family")
     ap.add_argument("--net", choices=("mlp", "convnet"), default="mlp", help="the reference's MLP line or its ConvNet line (main.py:72)")
     ap.add_argument("--channels", type=int, default=16, help="ConvNet: channels of the CrossConv tower")
     ap.add_argument("--depth", type=int, default=2, help="ConvNet: residual blocks")
@@ -72,6 +74,7 @@ if __name__ == "__main__":
             net_params=net_params,
         )
         trial.compact_log = args.compact_log
+        trial.obs_half = args.obs_half
         if args.lazy_rows:
             trial.lazy_rows = True
         if args.fused_tail:

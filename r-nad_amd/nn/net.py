@@ -14,7 +14,9 @@ State-dict keys (`value_fc0.weight`, ...) are the reference's, so its checkpoint
 ConvNet (reference nn/net.py:88-269): the CrossConv tower with a policy and a value head.  With batch_norm=False on the GPU the
 whole tower and both heads are ONE fp32-MFMA kernel over a row list (csrc/conv_tower.hip: every CrossConv as two products with
 Toeplitz-expanded weights), with rnad_conv_backward as its autograd backward; everything else -- CPU tensors, batch_norm=True,
-non-fp32 weights, shapes rnad_conv_supported declines -- runs the plain torch modules.
+non-fp32 weights, shapes rnad_conv_supported declines -- runs the plain torch modules.  Observations may be fp16 for either family
+(RNaD.obs_half, Episodes(obs_half=True)): an fp16 table holds rounded values, the kernels convert an element as they load it and
+compute in fp32, so both families give on an fp16 table what they give on the up-converted one, and no fp32 copy is made.
 
 Both classes expose the same small interface to learn/rnad.py and environment/episode.py (per_row_ready, pack_many, packed_size,
 tables_forward, table_forward, backward_rows, ROW_EXTRAS, ROLLOUT_KERNEL; for lazy rows: lazy_rows_ready, LAZY_ROWS_AUTO, staged_actor,
@@ -338,11 +340,11 @@ class ConvNet(nn.Module):
     def forward_logits(self, input_batch, want_logits=True, want_value=True, packed=None, live=None):
         """obs [N, 2, A, A] -> logits [N, A], value [N, 1]   (net.py:215-221,225).
 
-        Fusable nets on fp32 GPU observations: ONE HIP kernel (rnad_conv_forward); under autograd an autograd node whose backward
-        is rnad_conv_backward.  live: an rnad_hip.LiveRows over the N samples -- the kernel evaluates those rows only and returns
+        Fusable nets on fp32 or fp16 GPU observations: ONE HIP kernel (rnad_conv_forward_obs); under autograd an autograd node whose
+        backward is rnad_conv_backward_obs.  live: an rnad_hip.LiveRows over the N samples -- the kernel evaluates those rows only and returns
         zeros elsewhere; the torch fallback ignores it and evaluates everything."""
         A = self.max_actions
-        if input_batch.is_cuda and input_batch.dtype == torch.float32 and self._fusable():
+        if input_batch.is_cuda and input_batch.dtype in (torch.float32, torch.float16) and self._fusable():
             obs = input_batch.contiguous()
             packed = packed if packed is not None else self.pack()
             if not torch.is_grad_enabled():
@@ -394,11 +396,11 @@ class ConvNet(nn.Module):
         A = self.max_actions
         logits = value = None
         tree = getattr(episodes, "tree", None)
-        if (tree is not None and self._fusable() and not getattr(episodes, "obs_half", False)
+        if (tree is not None and self._fusable()
                 and episodes.indices.dtype == torch.int32 and episodes.indices.is_cuda and B <= 2**21):
             handle = tree.handle()
             if 8 * handle.S <= T * B:
-                table = handle.observations_table(False)
+                table = handle.observations_table(getattr(episodes, "obs_half", False))
                 idx = episodes.indices[:T].contiguous()
                 if torch.is_grad_enabled():
                     logits, value = rnad_hip.TabularConv.apply(table, idx, handle, self._shape(), self.pack(), *self._weights())

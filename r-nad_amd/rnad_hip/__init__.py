@@ -585,6 +585,13 @@ class FusedMLPRows(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------------------- fused ConvNet
+def _conv_obs_half(obs, who):
+    """The obs_half flag of the rnad_conv_*_obs entry points: fp32 or fp16 observations, nothing else (and never a converted copy)."""
+    if obs.dtype not in (F32, F16):
+        raise RnadHipError(f"{who}: fp32 or fp16 observations only, got {obs.dtype}")
+    return obs.dtype == F16
+
+
 def conv_supported(A, Ch, depth):
     """True when the CrossConv tower kernels (csrc/conv_tower.hip) cover the shape."""
     return bool(lib().rnad_conv_supported(A, Ch, depth))
@@ -609,10 +616,9 @@ def conv_pack(weights, A, Ch, depth, out=None):
 
 
 def conv_forward(packed, A, Ch, depth, obs, want_logits=True, want_value=True, live=None, out=None, zero_rest=True):
-    """packed: conv_pack(...); obs [N, 2, A, A] fp32 -> logits [N, A], value [N, 1] (rnad_conv_forward: tower and heads in one launch).
-    live / out / zero_rest: as mlp_forward."""
-    if obs.dtype != F32:
-        raise RnadHipError("conv_forward: fp32 observations only")
+    """packed: conv_pack(...); obs [N, 2, A, A] fp32 or fp16 -> logits [N, A], value [N, 1] (rnad_conv_forward_obs: tower and heads in one
+    launch; fp16 elements are converted as the kernel loads a tile).  live / out / zero_rest: as mlp_forward."""
+    half = _conv_obs_half(obs, "conv_forward")
     N = obs.numel() // (2 * A * A)
     alloc = torch.zeros if (live is not None and zero_rest) else torch.empty
     if out is not None:
@@ -624,33 +630,33 @@ def conv_forward(packed, A, Ch, depth, obs, want_logits=True, want_value=True, l
     assert live is None or live.N == N, "live-row list built for a different batch"
     if live is not None and live.rows.numel() == 0:  # (a list without capacity has no storage to point at: nothing is listed)
         return logits, value
-    _check(lib().rnad_conv_forward(C.c_int64(N), *_row_list(live), A, Ch, depth, _dp(packed, F32, "packed"), _dp(obs, F32, "obs"),
-                                   _dp(logits, F32, "logits", True), _dp(value, F32, "value", True), _stream()))
+    _check(lib().rnad_conv_forward_obs(C.c_int64(N), *_row_list(live), A, Ch, depth, _dp(packed, F32, "packed"),
+                                       _dp(obs, F16 if half else F32, "obs"), int(half), _dp(logits, F32, "logits", True),
+                                       _dp(value, F32, "value", True), _stream()))
     return logits, value
 
 
 def conv_forward_actor(tree, packed, A, Ch, depth, obs, logits, value, policy_rows, rows=None):
-    """rnad_conv_forward_actor: the ConvNet on (the listed rows of) the tree's observation table -> `logits` [2S, A] and `value` [2S, 1] (the
+    """rnad_conv_forward_actor_obs: the ConvNet on (the listed rows of) the tree's observation table, fp32 or fp16 -> `logits` [2S, A] and `value` [2S, 1] (the
     bits of conv_forward) and, from the kernel's epilogue, `policy_rows` [2S, policy row stride] -- the actor table of bucket_sort /
     bucket_play(table_is_policy=True).  Rows that are not listed are left alone in all three."""
-    if obs.dtype != F32:
-        raise RnadHipError("conv_forward_actor: fp32 observations only")
+    half = _conv_obs_half(obs, "conv_forward_actor")
     N = 2 * tree.S
     assert A == tree.A and obs.numel() == N * 2 * A * A
     assert logits.shape == (N, A) and value.numel() == N and policy_rows.shape[0] == N
     assert rows is None or rows.N == N
     if rows is not None and rows.rows.numel() == 0:  # (a list without capacity has no storage to point at: nothing is listed)
         return
-    _check(lib().rnad_conv_forward_actor(tree.ptr, *_row_list(rows), Ch, depth, _dp(packed, F32, "packed"), _dp(obs, F32, "obs"),
-                                         _dp(logits, F32, "logits"), _dp(value, F32, "value"), _dp(policy_rows, F32, "policy_rows"), _stream()))
+    _check(lib().rnad_conv_forward_actor_obs(tree.ptr, *_row_list(rows), Ch, depth, _dp(packed, F32, "packed"),
+                                             _dp(obs, F16 if half else F32, "obs"), int(half), _dp(logits, F32, "logits"),
+                                             _dp(value, F32, "value"), _dp(policy_rows, F32, "policy_rows"), _stream()))
 
 
 def conv_backward(packed, weights, A, Ch, depth, obs, dlogits, dvalue, live=None, out=None, capacity=None):
-    """Gradients of every ConvNet tensor for dL/dlogits [N, A], dL/dvalue [N(,1)] (rnad_conv_backward) -> views, shaped like
+    """Gradients of every ConvNet tensor for dL/dlogits [N, A], dL/dvalue [N(,1)] (rnad_conv_backward_obs; obs fp32 or fp16) -> views, shaped like
     `weights`, of ONE flat bucket in net.parameters() order (out: that bucket, preallocated -- e.g. the all-reduce buffer).
     live: a row list -- only those rows contribute.  capacity: the length of a FIXED row list (as mlp_backward)."""
-    if obs.dtype != F32:
-        raise RnadHipError("conv_backward: fp32 observations only")
+    half = _conv_obs_half(obs, "conv_backward")
     N = obs.numel() // (2 * A * A)
     n = conv_param_count(A, Ch, depth)
     assert sum(w.numel() for w in weights) == n
@@ -661,9 +667,9 @@ def conv_backward(packed, weights, A, Ch, depth, obs, dlogits, dvalue, live=None
     if live is not None and live.rows.numel() == 0:
         cap, live = 0, None  # (a list without capacity: no rows contribute, the gradients are zeros)
     ws = torch.empty((max(int(lib().rnad_conv_backward_workspace(C.c_int64(cap), A, Ch, depth)) // 4, 1),), dtype=F32, device=obs.device)
-    _check(lib().rnad_conv_backward(C.c_int64(cap), *_row_list(live), A, Ch, depth, _dp(packed, F32, "packed"), _dp(obs, F32, "obs"),
-                                    _dp(dlogits, F32, "dlogits"), _dp(dvalue, F32, "dvalue"), _dp(flat, F32, "grads"),
-                                    _dp(ws, F32, "workspace"), _stream()))
+    _check(lib().rnad_conv_backward_obs(C.c_int64(cap), *_row_list(live), A, Ch, depth, _dp(packed, F32, "packed"),
+                                        _dp(obs, F16 if half else F32, "obs"), int(half), _dp(dlogits, F32, "dlogits"), _dp(dvalue, F32, "dvalue"),
+                                        _dp(flat, F32, "grads"), _dp(ws, F32, "workspace"), _stream()))
     grads, at = [], 0
     for w in weights:
         grads.append(flat[at:at + w.numel()].view(w.shape))

@@ -16,6 +16,11 @@ the configs[1] tree, with the rows each step ran on.  The two trainers of a tree
 (RNaD.fused_optimizer = True: rnad_conv_optimizer_step, which also keeps the packed images current) off and on -- on the configs[1] tree, and
 with lazy rows on the configs[3]-shaped A = 5 tree of --lazy -- each with the kernel launches of one step.
 
+--obs-half runs a fourth leg instead (default --out profiles/convnet_half.md): the forward of net + target and the backward on the
+configs[1] tree, all rows and distinct observations, on the fp32 and on the fp16 observation table (the same kernels instantiated on the
+element type of the table: rnad_conv_forward_obs / rnad_conv_backward_obs), and one default ConvNet train_step with RNaD.obs_half off
+and on.  The windows of the two tables alternate; nothing gates the ratio.
+
 Times are device events around `reps` back-to-back calls after a warm-up of the same shapes; fused and torch windows alternate.  Needs the GPU: there is no CPU path.
 """
 import argparse
@@ -214,6 +219,101 @@ def tail_leg(args, dev):
     print(text)
 
 
+def spread(ms):
+    return f"{sum(ms) / len(ms):.4f} ({min(ms):.4f} .. {max(ms):.4f})"
+
+
+def half_leg(args, dev):
+    """The tower kernels and one default ConvNet train_step on the fp32 and on the fp16 observation table: ms (mean and spread over
+    alternating windows) per side, and the fp16 / fp32 ratio."""
+    os.environ["RNAD_SAVE_DIR"] = tempfile.mkdtemp(prefix="rnad_conv_half_")
+    out = args.out or os.path.join(ROOT, "profiles", "convnet_half.md")
+    torch.manual_seed(0)
+    A = 3
+    tree = Tree(device=dev, max_actions=A, max_transitions=1, depth_bound=6, transition_threshold=0.0)
+    tree.generate_native(seed=0)
+    handle = tree.handle()
+    tables = {False: handle.observations_table(False), True: handle.observations_table(True)}
+    dedups = {False: handle.obs_dedup(False), True: handle.obs_dedup(True)}
+    N = tables[False].shape[0]
+    shape = (A, args.channels, args.depth)
+    net = ConvNet(*shape, batch_norm=False, device=dev)
+    target = copy.deepcopy(net)
+    assert net._fusable(), "this shape is declined by rnad_conv_supported: nothing to time"
+    packed, packed_t = net.pack(), target.pack()
+    dl, dv = torch.randn((N, A), device=dev), torch.randn((N, 1), device=dev)
+    lines = [f"# ConvNet tower kernels on an fp32 and on an fp16 observation table, A = {A}, channels = {args.channels}, depth = {args.depth}, "
+             f"configs[1] tree ({N} rows)", "",
+             f"Build {rnad_hip.source_hash()}.  Device events around back-to-back calls; every window lasts about {WINDOW_MS / 1000:g} s after a warm-up of "
+             f"the same shapes; the windows of the two tables alternate, {args.rounds} rounds; a figure is the mean over the rounds, with the smallest "
+             "and the largest round beside it.  The fp16 kernels load the table as `__half2` pairs, converted with `__half22float2` as the "
+             "tile is staged; the activations and all arithmetic are fp32 on both sides.", "",
+             "| what | rows (fp32 / fp16 table) | fp32 table ms (min .. max) | fp16 table ms (min .. max) | fp16 / fp32 |", "|---|---|---|---|---|"]
+    notes = []
+
+    def row(what, rows, ms):
+        ratio = (sum(ms[True]) / len(ms[True])) / (sum(ms[False]) / len(ms[False]))
+        lines.append(f"| {what} | {rows} | {spread(ms[False])} | {spread(ms[True])} | {ratio:.3f} |")
+        print(lines[-1], flush=True)
+        # slower by more than the rounds of either side differ among themselves
+        noise = max(max(ms[k]) - min(ms[k]) for k in (False, True))
+        if sum(ms[True]) / len(ms[True]) - sum(ms[False]) / len(ms[False]) > noise:
+            notes.append(f"- {what}: the fp16 table is SLOWER by more than the spread between rounds ({ratio:.3f}x).")
+
+    for what, distinct in (("all rows", False), ("distinct observations", True)):
+        lives = {h: (dedups[h].uniq if distinct else None) for h in (False, True)}
+        counts = {h: (dedups[h].n_unique if distinct else N) for h in (False, True)}
+
+        def forward(h):
+            for p in (packed, packed_t):
+                rnad_hip.conv_forward(p, *shape, tables[h], live=lives[h], zero_rest=False)
+
+        def backward(h):
+            rnad_hip.conv_backward(packed, net._weights(), *shape, tables[h], dl, dv, live=lives[h], capacity=counts[h] if distinct else None)
+
+        for kind, fn in (("forward, net + target", forward), ("backward", backward)):
+            ms = {False: [], True: []}
+            for _ in range(args.rounds):
+                for h in (False, True):
+                    ms[h].append(timeit(lambda: fn(h), args.reps))
+            row(f"{kind}, {what}", f"{counts[False]} / {counts[True]}", ms)
+    B = 1 << args.lanes_log2
+    legs = {}
+    for h in (False, True):
+        torch.manual_seed(0)
+        rn = RNaD(tree=tree, device=dev, directory_name=f"half_{h}", batch_size=B, eta=0.2, b1_adam=0.0, lr=5e-5,
+                  net_params={"type": "ConvNet", "max_actions": A, "channels": args.channels, "depth": args.depth, "batch_norm": False})
+        rn.initialize()
+        rn.obs_half = h
+        buf = Buffer(1)
+
+        def step(rn=rn, buf=buf):
+            rn.train_step(buf, alpha=0.5)
+            rn.total_steps += 1
+
+        for _ in range(8):  # eager warm-up and the graph capture
+            step()
+        torch.cuda.synchronize()
+        legs[h] = (rn, step, [])
+    for _ in range(args.rounds):
+        for h in (False, True):
+            legs[h][2].append(timeit(legs[h][1], args.steps))
+    replay = all(bool(getattr(legs[h][0], "_graph", None) and legs[h][0]._graph.get("graph") is not None) for h in (False, True))
+    row(f"one default train_step, 2^{args.lanes_log2} lanes (hipGraph replay on both sides: {replay})", f"{N} / {N}", {h: legs[h][2] for h in (False, True)})
+    lines += ["", "Nothing gates the ratio: the tower is bound by LDS traffic, and the table is read once per tile.  The fp16 table is half the "
+              f"bytes of the fp32 one ({tables[True].numel() * 2} against {tables[False].numel() * 4})."]
+    lines += [""] + (notes or ["On no line is the fp16 table slower than the fp32 table by more than the spread between rounds."])
+    text = "\n".join(lines) + "\n"
+    # the registers / scratch of the instantiations are read from the code object's metadata, not measured here: that section is kept
+    marker, kept = "## Code object resources", ""
+    if os.path.exists(out):
+        old = open(out).read()
+        kept = old[old.index(marker):] if marker in old else ""
+    with open(out, "w") as f:
+        f.write(text + ("\n" + kept if kept else ""))
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", type=int, default=16)
@@ -226,6 +326,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-torch", action="store_true", help="leave the torch-module baseline out")
     ap.add_argument("--lazy", action="store_true", help="only the lazy-rows leg: a ConvNet train_step with lazy_rows off and on, on two trees")
+    ap.add_argument("--obs-half", action="store_true", help="only the fp16-table leg: the tower kernels and a ConvNet train_step on the fp32 and the fp16 observation table")
     ap.add_argument("--tail", action="store_true", help="only the optimiser-tail leg: a ConvNet train_step with RNaD.fused_optimizer off and on, on two trees")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "conv_bench needs the MI355X"
@@ -234,6 +335,8 @@ def main():
         return lazy_leg(args, dev)
     if args.tail:
         return tail_leg(args, dev)
+    if args.obs_half:
+        return half_leg(args, dev)
     torch.manual_seed(0)
     A = 3
     tree = Tree(device=dev, max_actions=A, max_transitions=1, depth_bound=6, transition_threshold=0.0)
