@@ -15,7 +15,8 @@
 // for the whole workgroup, and are added into 16 LDS copies of that row.  No global atomic on the common path, results in 64-bit fixed
 // point (integer sums: any order, same bits).  On a regular tree the cut is a level; on a pruned one it follows the subtrees.
 //
-//   k_bucket_keys      lane-ordered: plays the env steps above the cut only, key = the group reached (or the upper state the lane ends in)
+//   k_bucket_keys      lane-ordered: plays the env steps above the cut only, key = the group reached (or the upper state the lane ends in);
+//                      k_bucket_keys_lds / k_bucket_keys_hybrid: the same walk with all / the top upper tables in LDS, plus the tile's histogram
 //   k_bucket_hist/scan/items/scatter   stable counting sort of the lanes by key (deterministic), work items per bucket
 //   k_bucket_rollout   bucket-ordered: thread j replays lane lane_ids[j] from the root (counter-based draws keyed by the GLOBAL lane
 //                      id, include/rnad_rng.h) and records the trajectory -- column j of every [T, B] buffer, or (COMPACT) of
@@ -23,6 +24,9 @@
 //   k_bucket_expand    the dense [T, B] buffers of a compact trajectory, when something asks for them
 //   k_bucket_learn     one workgroup per work item: backward-in-time V-trace / NeuRD pass per lane (learn_math.hpp; COMPACT:
 //                      fast_slot on row-precomputed operands), sums in LDS
+//   k_bucket_rollout_items<A, REL> / k_bucket_learn_c<A, REL, LOSSES, WEIGHTED>   the default step's pair: one workgroup per work item, the
+//                      compact trajectory only; k_bucket_play_learn<A, REL, DISTINCT> is both in one launch, k_bucket_play_count the
+//                      rollout half of the leaf-path step
 //   k_policy_rows / k_row_records   everything that depends on the (player, state) row alone, once per row instead of per slot
 //   k_bucket_finish    fixed point -> fp32 tables dL/dlogit [2S, A], dL/dv [2S], normalised by the batch-global N_P
 #include "learn_math.hpp"
@@ -44,10 +48,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxPath = 32;         // env steps above a group (path rows of the LDS table)
-#ifndef RNAD_PATH_SLOTS
-#define RNAD_PATH_SLOTS 16
-#endif
-constexpr int kPathSlots = RNAD_PATH_SLOTS;  // copies of a path row in LDS: lane l adds into copy l & 15 (4-way instead of 64-way same-address adds)
+constexpr int kPathSlots = 16;       // copies of a path row in LDS: lane l adds into copy l & 15 (4-way instead of 64-way same-address adds)
 constexpr int kMaxBuckets = 12288;   // LDS histogram of the sort passes: 48 KiB of int32
 constexpr int kMaxUpper = 8192;      // upper states (64 replicas of their rows are kept)
 constexpr int kSortThreads = 1024;   // threads per block of the sort passes
@@ -66,20 +67,16 @@ constexpr int kTicketGroups = 64;     // first-level tickets of k_bucket_finish'
 constexpr int kTargetLanes = 1024;   // finest cut whose groups still hold this many lanes on average (configs[1]: full work items win)
 constexpr int kMinLanesLevelCut = 128;  // a level cut (one group per subtree) is taken while its groups hold this many lanes on average
 
-// lanes per thread of the walks with tables in LDS (k_bucket_keys_lds, k_bucket_keys_hybrid).  r04: one lane per thread -- 18.9 -> 17.7 us on
-// configs[1], 42.9 -> 37.8 on configs[3]'s hybrid walk (two: what the global-table walk above keeps; four: 18.3 / 46.1)
-#ifndef RNAD_PLAY_LDS
-#define RNAD_PLAY_LDS 1
-#endif
-constexpr int kPlayLds = RNAD_PLAY_LDS;
-constexpr int kMinSortTile = kSortThreads * kPlayLds > 1024 ? kSortThreads * kPlayLds : 1024;  // a tile is a whole number of passes of the LDS walks
+// The walks with tables in LDS (k_bucket_keys_lds, k_bucket_keys_hybrid) play one lane per thread.  r04: 18.9 -> 17.7 us on configs[1],
+// 42.9 -> 37.8 on configs[3]'s hybrid walk against two lanes (what the global-table walk keeps); four: 18.3 / 46.1.
+constexpr int kMinSortTile = 1024;  // a tile is a whole number of passes (kSortThreads lanes each) of the LDS walks
 // `kTile` = the plan's sort tile as a constant (tiles below kMinSortTile are never planned)
-#define RNAD_DISPATCH_TILE(p_, ...)                                                          \
-    switch ((p_).tile) {                                                                     \
-        case 1024: { constexpr int kTile = kMinSortTile > 1024 ? kMinSortTile : 1024; __VA_ARGS__; } break; \
-        case 2048: { constexpr int kTile = kMinSortTile > 2048 ? kMinSortTile : 2048; __VA_ARGS__; } break; \
-        case 8192: { constexpr int kTile = 8192; __VA_ARGS__; } break;                        \
-        default: { constexpr int kTile = kSortLanes; __VA_ARGS__; } break;                    \
+#define RNAD_DISPATCH_TILE(p_, ...)                                         \
+    switch ((p_).tile) {                                                    \
+        case 1024: { constexpr int kTile = 1024; __VA_ARGS__; } break;      \
+        case 2048: { constexpr int kTile = 2048; __VA_ARGS__; } break;      \
+        case 8192: { constexpr int kTile = 8192; __VA_ARGS__; } break;      \
+        default: { constexpr int kTile = kSortLanes; __VA_ARGS__; } break;  \
     }
 
 inline unsigned blocks_for(int64_t n, int per = kThreads) { return (unsigned)((n + per - 1) / per); }
@@ -559,10 +556,84 @@ struct StageOut {
 constexpr int kStageRootBits = 26;  // S <= 2^26 states; kMaxPath = 32 steps fit the 6 bits above
 __host__ __device__ inline uint32_t stage_stamp(uint64_t seed) { return ((uint32_t)seed ^ (uint32_t)(seed >> 32)) | 1u; }
 
-#ifndef RNAD_PLAY
-#define RNAD_PLAY 2
-#endif
-constexpr int kPlay = RNAD_PLAY;
+constexpr int kPlay = 2;  // lanes per thread of the global-table walk (its measured winner; the LDS walks play one)
+
+// What every keys walk keeps per lane, and what it stores for it: the one statement of the bookkeeping the three kernels below share.
+// decisions: what a lane drew at its first kPackedSteps env steps -- 3 bits of action and 3 bits of chance outcome per step, the number of
+// steps recorded in the top 4 bits -- so that k_bucket_rollout replays them without drawing again.
+struct KeysLane {
+    int state, key, steps;      // the state the lane stands in, its bucket so far, the env steps it played above the cut
+    unsigned long long packed;  // the decisions of those steps
+    bool on;                    // still in an upper state
+
+    __device__ __forceinline__ void start(bool in_batch, int key_root, int n_groups) {
+        state = 1;
+        key = key_root;
+        steps = 0;
+        packed = 0ull;
+        on = in_batch && key_root >= n_groups;
+    }
+    // position of the lane's upper state among the upper states (a lane that has stopped: 0)
+    __device__ __forceinline__ int upper_slot(int n_groups) const { return on ? key - n_groups : 0; }
+    // the row player's action, drawn at step t
+    __device__ __forceinline__ void row_action(int t, int a0) {
+        if (on) {
+            if (t < kPackedSteps) packed |= (unsigned long long)a0 << (6 * t);
+            steps = t + 1;
+        }
+    }
+    // the column player's action and the chance outcome, drawn at step t + 1: the lane moves to `next`, a state of bucket key_next
+    __device__ __forceinline__ void move(int t, int a1, int chosen, int next, int key_next, int n_groups) {
+        if (on) {
+            if (t + 1 < kPackedSteps) packed |= (unsigned long long)(a1 | (chosen << 3)) << (6 * (t + 1));
+            steps = t + 2;
+            state = next;
+            if (next != 0) key = key_next;  // (a lane that leaves the tree from an upper state keeps that state's bucket)
+            on = next != 0 && key_next >= n_groups;
+        }
+    }
+    // lane b's outputs (b < B)
+    __device__ __forceinline__ void store(int64_t b, int n_groups, uint64_t seed, int32_t *__restrict__ keys,
+                                          unsigned long long *__restrict__ decisions, const StageOut &stage) const {
+        keys[b] = key;
+        decisions[b] = packed | ((unsigned long long)min(steps, kPackedSteps) << 60);
+        if (stage.root) {  // (state: where the walk stopped -- the root of a group subtree when the key is a group)
+            const int root = key < n_groups ? state : 0;
+            stage.root[b] = (uint32_t)root | ((uint32_t)steps << kStageRootBits);
+            if (root) stage.mark0[root] = stage_stamp(seed);
+        }
+    }
+};
+
+// The prologue of every keys walk: the sums this rollout ends with start at zero, and the step's seed.
+__device__ __forceinline__ uint64_t keys_prologue(double *__restrict__ norm, const StageOut &stage, const rnad_step_params_t *__restrict__ sp,
+                                                  uint64_t seed) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (norm) norm[0] = norm[1] = 0.0;  // summed up by k_bucket_alive at the end of this rollout
+        if (stage.counts) stage.counts[0] = stage.counts[1] = 0ull;
+    }
+    return sp ? sp->seed : seed;  // per-step scalars in device memory: a captured graph of the step replays with new values
+}
+
+// The column player's action and the chance outcome through the tables of upper slot `sl` staged in LDS (k_bucket_keys_lds, the hot
+// branch of k_bucket_keys_hybrid): pol [slots][2][kPolStride<A>] policy rows, w [slots][A][A][C] outcomes.  (The row player's row is
+// row 2 * sl of pol; the hybrid walk picks from it or from a global row with one copy of pick's arithmetic, so that stays with the kernels.)
+template <int A>
+__device__ __forceinline__ UpperWalk lds_transition(const UpperWalk *w, const float *pol, int C, int sl, int a0, float u_col, float u_chance,
+                                                    int &a1, int &chosen) {
+    float p1[A];
+    load_policy_row<A>(pol, (int64_t)sl * 2 + 1, kPolStride<A>, true, p1);
+    a1 = pick<A>(p1, u_col);
+    const UpperWalk *e = w + ((sl * A + a0) * A + a1) * C;
+    chosen = 0;
+    if (C > 1) {
+        float ch[RNAD_MAX_TRANSITIONS];
+#pragma unroll
+        for (int k = 0; k < RNAD_MAX_TRANSITIONS; ++k) ch[k] = k < C ? e[k].chance : 0.0f;
+        chosen = pick_n<RNAD_MAX_TRANSITIONS>(C, ch, u_chance);
+    }
+    return e[chosen];
+}
 
 template <int A, int L>
 __global__ __launch_bounds__(kThreads) void k_bucket_keys(const Trans *__restrict__ trans, int C, int64_t S, int64_t B, int n_steps,
@@ -572,34 +643,23 @@ __global__ __launch_bounds__(kThreads) void k_bucket_keys(const Trans *__restric
                                                           int32_t *__restrict__ keys, unsigned long long *__restrict__ decisions,
                                                           double *__restrict__ norm, StageOut stage) {
     const int64_t b0 = (int64_t)blockIdx.x * (kThreads * L) + threadIdx.x;  // this thread's lanes: b0 + l * kThreads
-    if (b0 == 0 && norm) norm[0] = norm[1] = 0.0;  // summed up by k_bucket_alive at the end of this rollout
-    if (b0 == 0 && stage.counts) stage.counts[0] = stage.counts[1] = 0ull;
-    if (sp) seed = sp->seed;  // per-step scalars in device memory: a captured graph of the step replays with new values
+    seed = keys_prologue(norm, stage, sp, seed);
     const int key_root = bucket_of[1];
-    // decisions: what a lane drew at its first kPackedSteps env steps -- 3 bits of action and 3 bits of chance outcome per step,
-    // the number of steps recorded in the top 4 bits -- so that k_bucket_rollout replays them without drawing again
-    int state[L], key[L], steps[L];
-    unsigned long long packed[L];
-    bool on[L];  // still in an upper state
+    KeysLane lane[L];
 #pragma unroll
-    for (int l = 0; l < L; ++l) {
-        state[l] = 1;
-        key[l] = key_root;
-        steps[l] = 0;
-        packed[l] = 0ull;
-        on[l] = b0 + (int64_t)l * kThreads < B && key_root >= n_groups;
-    }
+    for (int l = 0; l < L; ++l) lane[l].start(b0 + (int64_t)l * kThreads < B, key_root, n_groups);
     for (int t = 0; t < n_steps; t += 2) {  // one game transition per iteration: both players' steps in `state`, then the chance draw
         bool any = false;
 #pragma unroll
-        for (int l = 0; l < L; ++l) any |= on[l];
+        for (int l = 0; l < L; ++l) any |= lane[l].on;
         if (!any) break;
         const bool two = t + 1 < n_steps;
         float u[L][3], pol0[L][A], pol1[L][A];
         int a0[L];
+        // every lane's loads first, then the draws
 #pragma unroll
         for (int l = 0; l < L; ++l) {
-            const int64_t st = on[l] ? state[l] : 0;
+            const int64_t st = lane[l].on ? lane[l].state : 0;
             load_policy_row<A>(policy_tab, st, tab_stride, vec4 != 0, pol0[l]);
             if (two) load_policy_row<A>(policy_tab, S + st, tab_stride, vec4 != 0, pol1[l]);
         }
@@ -608,10 +668,7 @@ __global__ __launch_bounds__(kThreads) void k_bucket_keys(const Trans *__restric
 #pragma unroll
         for (int l = 0; l < L; ++l) {
             a0[l] = pick<A>(pol0[l], u[l][0]);
-            if (on[l]) {
-                if (t < kPackedSteps) packed[l] |= (unsigned long long)a0[l] << (6 * t);
-                steps[l] = t + 1;
-            }
+            lane[l].row_action(t, a0[l]);
         }
         if (!two) break;
 #pragma unroll
@@ -619,29 +676,14 @@ __global__ __launch_bounds__(kThreads) void k_bucket_keys(const Trans *__restric
             const int a1 = pick<A>(pol1[l], u[l][1]);
             int next, chosen = 0;
             float rew;
-            transition_lane<A>(trans, C, on[l] ? state[l] : 0, a0[l], a1, nullptr, u[l][2], next, rew, &chosen);
-            const int key_next = bucket_of[next];
-            if (on[l]) {
-                if (t + 1 < kPackedSteps) packed[l] |= (unsigned long long)(a1 | (chosen << 3)) << (6 * (t + 1));
-                steps[l] = t + 2;
-                state[l] = next;
-                if (next != 0) key[l] = key_next;  // (a lane that leaves the tree from an upper state keeps that state's bucket)
-                on[l] = next != 0 && key_next >= n_groups;
-            }
+            transition_lane<A>(trans, C, lane[l].on ? lane[l].state : 0, a0[l], a1, nullptr, u[l][2], next, rew, &chosen);
+            lane[l].move(t, a1, chosen, next, bucket_of[next], n_groups);
         }
     }
 #pragma unroll
     for (int l = 0; l < L; ++l) {
         const int64_t b = b0 + (int64_t)l * kThreads;
-        if (b < B) {
-            keys[b] = key[l];
-            decisions[b] = packed[l] | ((unsigned long long)min(steps[l], kPackedSteps) << 60);
-            if (stage.root) {  // (state: where the walk stopped -- the root of a group subtree when the key is a group)
-                const int root = key[l] < n_groups ? state[l] : 0;
-                stage.root[b] = (uint32_t)root | ((uint32_t)steps[l] << kStageRootBits);
-                if (root) stage.mark0[root] = stage_stamp(seed);
-            }
-        }
+        if (b < B) lane[l].store(b, n_groups, seed, keys, decisions, stage);
     }
 }
 
@@ -684,7 +726,7 @@ inline size_t keys_lds_bytes(int n_upper, int n_buckets, int A, int C) {
            (size_t)n_buckets * sizeof(int32_t);
 }
 
-template <int A, int L, int TILE>
+template <int A, int TILE>
 __global__ __launch_bounds__(kSortThreads) void k_bucket_keys_lds(const UpperWalk *__restrict__ walk, const int32_t *__restrict__ upper_list,
                                                                   int n_upper, int n_buckets, int C, int64_t S, int64_t B, int n_steps,
                                                                   const float *__restrict__ policy_tab, int64_t tab_stride, int key_root,
@@ -708,83 +750,35 @@ __global__ __launch_bounds__(kSortThreads) void k_bucket_keys_lds(const UpperWal
     // (r04 made the copies here, "in flight during the walk": 19 MB through the B / 4096 workgroups of this launch -- 64 of them at 2^18
     // lanes, 27 us where the walk alone takes 9.  r05: extra workgroups of the scan launch that follows, k_bucket_scan)
     for (int i = threadIdx.x; i < n_buckets; i += kSortThreads) cnt[i] = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && norm) norm[0] = norm[1] = 0.0;  // summed up by k_bucket_alive at the end of this rollout
-    if (blockIdx.x == 0 && threadIdx.x == 0 && stage.counts) stage.counts[0] = stage.counts[1] = 0ull;
-    if (sp) seed = sp->seed;
+    seed = keys_prologue(norm, stage, sp, seed);
     __syncthreads();
-    static_assert(TILE % (kSortThreads * L) == 0, "a sort tile is a whole number of passes");
-    for (int pass = 0; pass < TILE / (kSortThreads * L); ++pass) {
-        const int64_t b0 = (int64_t)blockIdx.x * TILE + (int64_t)pass * (kSortThreads * L) + threadIdx.x;  // lanes b0 + l * kSortThreads
-        int slot[L], key[L], steps[L], root[L];
-        unsigned long long packed[L];
-        bool on[L];
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            root[l] = key_root < n_groups ? 1 : 0;  // (a tree that is one group: every lane enters it at state 1)
-            slot[l] = key_root - n_groups;
-            key[l] = key_root;
-            steps[l] = 0;
-            packed[l] = 0ull;
-            on[l] = b0 + (int64_t)l * kSortThreads < B && key_root >= n_groups;
-        }
+    static_assert(TILE % kSortThreads == 0, "a sort tile is a whole number of passes");
+    // (the two passes of a 2048-lane tile unrolled, four and eight passes as a loop: stated, because this body sits right at the
+    // unroller's size threshold for A = 2 and 3 -- configs[1]'s 4096-lane tile is timed as a loop)
+    constexpr int kPasses = TILE / kSortThreads, kUnroll = kPasses <= 2 ? kPasses : 1;
+#pragma unroll kUnroll
+    for (int pass = 0; pass < kPasses; ++pass) {
+        const int64_t b = (int64_t)blockIdx.x * TILE + (int64_t)pass * kSortThreads + threadIdx.x;
+        KeysLane lane;
+        lane.start(b < B, key_root, n_groups);
         for (int t = 0; t < n_steps; t += 2) {
-            bool any = false;
-#pragma unroll
-            for (int l = 0; l < L; ++l) any |= on[l];
-            if (!any) break;
+            if (!lane.on) break;
             const bool two = t + 1 < n_steps;
-            float u[L][3];
-            int a0[L];
-#pragma unroll
-            for (int l = 0; l < L; ++l) rnad_decision_uniforms(seed, (uint64_t)(lane0 + b0 + (int64_t)l * kSortThreads), (uint32_t)t, u[l]);
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                float p0[A];
-                load_policy_row<A>(pol, (int64_t)(on[l] ? slot[l] : 0) * 2, PS, true, p0);
-                a0[l] = pick<A>(p0, u[l][0]);
-                if (on[l]) {
-                    if (t < kPackedSteps) packed[l] |= (unsigned long long)a0[l] << (6 * t);
-                    steps[l] = t + 1;
-                }
-            }
+            float u[3];
+            rnad_decision_uniforms(seed, (uint64_t)(lane0 + b), (uint32_t)t, u);
+            const int sl = lane.upper_slot(n_groups);
+            float p0[A];
+            load_policy_row<A>(pol, (int64_t)sl * 2, PS, true, p0);
+            const int a0 = pick<A>(p0, u[0]);
+            lane.row_action(t, a0);
             if (!two) break;
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                const int sl = on[l] ? slot[l] : 0;
-                float p1[A];
-                load_policy_row<A>(pol, (int64_t)sl * 2 + 1, PS, true, p1);
-                const int a1 = pick<A>(p1, u[l][1]);
-                const UpperWalk *e = w + ((sl * A + a0[l]) * A + a1) * C;
-                int chosen = 0;
-                if (C > 1) {
-                    float ch[RNAD_MAX_TRANSITIONS];
-#pragma unroll
-                    for (int k = 0; k < RNAD_MAX_TRANSITIONS; ++k) ch[k] = k < C ? e[k].chance : 0.0f;
-                    chosen = pick_n<RNAD_MAX_TRANSITIONS>(C, ch, u[l][2]);
-                }
-                const UpperWalk hit = e[chosen];
-                if (on[l]) {
-                    if (t + 1 < kPackedSteps) packed[l] |= (unsigned long long)(a1 | (chosen << 3)) << (6 * (t + 1));
-                    steps[l] = t + 2;
-                    if (hit.next != 0) key[l] = hit.key;  // (a lane that leaves the tree from an upper state keeps that state's bucket)
-                    on[l] = hit.next != 0 && hit.key >= n_groups;
-                    slot[l] = on[l] ? hit.key - n_groups : 0;
-                    if (hit.next != 0 && hit.key < n_groups) root[l] = hit.next;
-                }
-            }
+            int a1, chosen;
+            const UpperWalk hit = lds_transition<A>(w, pol, C, sl, a0, u[1], u[2], a1, chosen);
+            lane.move(t, a1, chosen, hit.next, hit.key, n_groups);
         }
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t b = b0 + (int64_t)l * kSortThreads;
-            if (b < B) {
-                keys[b] = key[l];
-                decisions[b] = packed[l] | ((unsigned long long)min(steps[l], kPackedSteps) << 60);
-                atomicAdd(&cnt[key[l]], 1);
-                if (stage.root) {
-                    stage.root[b] = (uint32_t)root[l] | ((uint32_t)steps[l] << kStageRootBits);
-                    if (root[l]) stage.mark0[root[l]] = stage_stamp(seed);
-                }
-            }
+        if (b < B) {
+            lane.store(b, n_groups, seed, keys, decisions, stage);
+            atomicAdd(&cnt[lane.key], 1);
         }
     }
     __syncthreads();
@@ -803,7 +797,7 @@ inline size_t keys_hybrid_lds_bytes(int n_hot, int n_upper, int A, int C) {
            (size_t)n_upper * sizeof(int32_t);
 }
 
-template <int A, int L, int TILE>
+template <int A, int TILE>
 __global__ __launch_bounds__(kSortThreads) void k_bucket_keys_hybrid(const UpperWalk *__restrict__ walk, const int32_t *__restrict__ upper_list,
                                                                      const int32_t *__restrict__ hot_list, const int32_t *__restrict__ hot_of_g,
                                                                      int n_hot, int n_upper, const Trans *__restrict__ trans,
@@ -816,8 +810,8 @@ __global__ __launch_bounds__(kSortThreads) void k_bucket_keys_hybrid(const Upper
                                                                      int32_t *__restrict__ hist) {
     extern __shared__ __attribute__((aligned(16))) unsigned char keys_smem[];
     constexpr int PS = kPolStride<A>;
-    constexpr int kPasses = TILE / (kSortThreads * L);
-    int my_keys[kPasses][L];
+    constexpr int kPasses = TILE / kSortThreads;
+    int my_keys[kPasses];  // the keys of this thread's lanes, for the histogram
     const int AAC = A * A * C;
     UpperWalk *w = reinterpret_cast<UpperWalk *>(keys_smem);                                                           // [n_hot][A][A][C]
     float *pol = reinterpret_cast<float *>(keys_smem + (((size_t)n_hot * AAC * sizeof(UpperWalk) + 15) & ~(size_t)15));  // [n_hot][2][PS]
@@ -828,96 +822,42 @@ __global__ __launch_bounds__(kSortThreads) void k_bucket_keys_hybrid(const Upper
         pol[i] = a < A ? policy_tab[((int64_t)player * S + upper_list[hot_list[h]]) * tab_stride + a] : 0.0f;
     }
     for (int i = threadIdx.x; i < n_upper; i += kSortThreads) hot_of[i] = hot_of_g[i];
-    if (blockIdx.x == 0 && threadIdx.x == 0 && norm) norm[0] = norm[1] = 0.0;  // summed up by k_bucket_alive at the end of this rollout
-    if (blockIdx.x == 0 && threadIdx.x == 0 && stage.counts) stage.counts[0] = stage.counts[1] = 0ull;
-    if (sp) seed = sp->seed;
+    seed = keys_prologue(norm, stage, sp, seed);
     __syncthreads();
 #pragma unroll
     for (int pass = 0; pass < kPasses; ++pass) {
-        const int64_t b0 = (int64_t)blockIdx.x * TILE + (int64_t)pass * (kSortThreads * L) + threadIdx.x;  // lanes b0 + l * kSortThreads
-        int state[L], hot[L], key[L], steps[L];  // hot: position of the lane's upper state in the staged tables, or -1
-        unsigned long long packed[L];
-        bool on[L];
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            state[l] = 1;
-            key[l] = key_root;
-            steps[l] = 0;
-            packed[l] = 0ull;
-            on[l] = b0 + (int64_t)l * kSortThreads < B && key_root >= n_groups;
-            hot[l] = on[l] ? hot_of[key_root - n_groups] : 0;
-        }
+        const int64_t b = (int64_t)blockIdx.x * TILE + (int64_t)pass * kSortThreads + threadIdx.x;
+        KeysLane lane;
+        lane.start(b < B, key_root, n_groups);
+        int hot = lane.on ? hot_of[lane.upper_slot(n_groups)] : 0;  // position of the lane's upper state in the staged tables, or -1
         for (int t = 0; t < n_steps; t += 2) {
-            bool any = false;
-#pragma unroll
-            for (int l = 0; l < L; ++l) any |= on[l];
-            if (!any) break;
+            if (!lane.on) break;
             const bool two = t + 1 < n_steps;
-            float u[L][3];
-            int a0[L];
-#pragma unroll
-            for (int l = 0; l < L; ++l) rnad_decision_uniforms(seed, (uint64_t)(lane0 + b0 + (int64_t)l * kSortThreads), (uint32_t)t, u[l]);
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                float p0[A];
-                if (!on[l] || hot[l] >= 0) load_policy_row<A>(pol, (int64_t)(on[l] ? hot[l] : 0) * 2, PS, true, p0);
-                else load_policy_row<A>(policy_tab, state[l], tab_stride, vec4 != 0, p0);
-                a0[l] = pick<A>(p0, u[l][0]);
-                if (on[l]) {
-                    if (t < kPackedSteps) packed[l] |= (unsigned long long)a0[l] << (6 * t);
-                    steps[l] = t + 1;
-                }
-            }
+            float u[3];
+            rnad_decision_uniforms(seed, (uint64_t)(lane0 + b), (uint32_t)t, u);
+            float p0[A];
+            if (hot >= 0) load_policy_row<A>(pol, (int64_t)hot * 2, PS, true, p0);
+            else load_policy_row<A>(policy_tab, lane.state, tab_stride, vec4 != 0, p0);
+            const int a0 = pick<A>(p0, u[0]);
+            lane.row_action(t, a0);
             if (!two) break;
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                int next, key_next, chosen = 0, a1;
-                if (!on[l] || hot[l] >= 0) {
-                    const int sl = on[l] ? hot[l] : 0;
-                    float p1[A];
-                    load_policy_row<A>(pol, (int64_t)sl * 2 + 1, PS, true, p1);
-                    a1 = pick<A>(p1, u[l][1]);
-                    const UpperWalk *e = w + ((sl * A + a0[l]) * A + a1) * C;
-                    if (C > 1) {
-                        float ch[RNAD_MAX_TRANSITIONS];
-#pragma unroll
-                        for (int k = 0; k < RNAD_MAX_TRANSITIONS; ++k) ch[k] = k < C ? e[k].chance : 0.0f;
-                        chosen = pick_n<RNAD_MAX_TRANSITIONS>(C, ch, u[l][2]);
-                    }
-                    const UpperWalk hit = e[chosen];
-                    next = hit.next;
-                    key_next = hit.key;
-                } else {
-                    float p1[A], rew;
-                    load_policy_row<A>(policy_tab, S + state[l], tab_stride, vec4 != 0, p1);
-                    a1 = pick<A>(p1, u[l][1]);
-                    transition_lane<A>(trans, C, state[l], a0[l], a1, nullptr, u[l][2], next, rew, &chosen);
-                    key_next = bucket_of[next];
-                }
-                if (on[l]) {
-                    if (t + 1 < kPackedSteps) packed[l] |= (unsigned long long)(a1 | (chosen << 3)) << (6 * (t + 1));
-                    steps[l] = t + 2;
-                    state[l] = next;
-                    if (next != 0) key[l] = key_next;  // (a lane that leaves the tree from an upper state keeps that state's bucket)
-                    on[l] = next != 0 && key_next >= n_groups;
-                    hot[l] = on[l] ? hot_of[key_next - n_groups] : 0;
-                }
+            int next, key_next, chosen = 0, a1;
+            if (hot >= 0) {
+                const UpperWalk hit = lds_transition<A>(w, pol, C, hot, a0, u[1], u[2], a1, chosen);
+                next = hit.next;
+                key_next = hit.key;
+            } else {
+                float p1[A], rew;
+                load_policy_row<A>(policy_tab, S + lane.state, tab_stride, vec4 != 0, p1);
+                a1 = pick<A>(p1, u[1]);
+                transition_lane<A>(trans, C, lane.state, a0, a1, nullptr, u[2], next, rew, &chosen);
+                key_next = bucket_of[next];
             }
+            lane.move(t, a1, chosen, next, key_next, n_groups);
+            hot = lane.on ? hot_of[lane.upper_slot(n_groups)] : 0;
         }
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t b = b0 + (int64_t)l * kSortThreads;
-            my_keys[pass][l] = b < B ? key[l] : -1;
-            if (b < B) {
-                keys[b] = key[l];
-                decisions[b] = packed[l] | ((unsigned long long)min(steps[l], kPackedSteps) << 60);
-                if (stage.root) {
-                    const int root = key[l] < n_groups ? state[l] : 0;
-                    stage.root[b] = (uint32_t)root | ((uint32_t)steps[l] << kStageRootBits);
-                    if (root) stage.mark0[root] = stage_stamp(seed);
-                }
-            }
-        }
+        my_keys[pass] = b < B ? lane.key : -1;
+        if (b < B) lane.store(b, n_groups, seed, keys, decisions, stage);
     }
     // the tile's histogram row, in the LDS the tables occupied
     __syncthreads();
@@ -926,9 +866,7 @@ __global__ __launch_bounds__(kSortThreads) void k_bucket_keys_hybrid(const Upper
     __syncthreads();
 #pragma unroll
     for (int pass = 0; pass < kPasses; ++pass)
-#pragma unroll
-        for (int l = 0; l < L; ++l)
-            if (my_keys[pass][l] >= 0) atomicAdd(&cnt[my_keys[pass][l]], 1);
+        if (my_keys[pass] >= 0) atomicAdd(&cnt[my_keys[pass]], 1);
     __syncthreads();
     int32_t *row = hist + (int64_t)blockIdx.x * n_buckets;
     for (int i = threadIdx.x; i < n_buckets; i += kSortThreads) row[i] = cnt[i];
@@ -959,17 +897,10 @@ __global__ __launch_bounds__(kSortThreads) void k_bucket_hist(int64_t B, int n_b
 // of fabric traffic per rollout launch on configs[1], 8 x 8.5 MB per learner launch).  Here XCD x takes the x-th CONTIGUOUS eighth of the
 // items, so its L2 only sees its eighth of the tree.  Bijective for any item count n (the grid holds n + 7 workgroups at least).
 // Returns -1 for a workgroup without an item.
-#ifndef RNAD_XCD_ITEMS
-#define RNAD_XCD_ITEMS 1
-#endif
 __device__ __forceinline__ int xcd_item(int n) {
-#if RNAD_XCD_ITEMS
     const int q = n >> 3, r = n & 7, xcd = (int)blockIdx.x & 7, k = (int)blockIdx.x >> 3;
     const int cnt = q + (xcd < r ? 1 : 0), start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return k < cnt ? start + k : -1;
-#else
-    return (int)blockIdx.x < n ? (int)blockIdx.x : -1;
-#endif
 }
 
 // The row list of staging level LEVEL: both players' rows of every state whose stamp (LEVEL 0: its own in mark0; LEVEL 1: its anchor's
@@ -1460,24 +1391,9 @@ __device__ __forceinline__ REL rel_of(int state, int lo) {
     return (REL)(state == 0 ? 0 : state - lo + 1);
 }
 
-// L lanes per thread (workgroups of kThreads / L threads, lanes l * NT + thread of the item's pass; build switch).  The kernel spends 59 %
-// of a resident wave's time on s_waitcnt with the SIMDs' wave slots full (41 VGPRs), so more independent chains per thread looked like
-// the lever -- measured on configs[1] / configs[3]: L = 1 27.0 / 61.8 us, L = 2 28.2 / 62.4, L = 4 36.8 / 80.3.  It is not the number of
-// lanes in flight that bounds it.
-#ifndef RNAD_ROLLOUT_LANES
-#define RNAD_ROLLOUT_LANES 1
-#endif
-constexpr int kRolloutLanes = RNAD_ROLLOUT_LANES;
-
-// What a thread of k_bucket_play_learn hands from its rollout to its update in registers (single-pass items: lane item.begin + thread):
-// the packed actions, the reward, the relative state of the last four stored transitions (16 bits each, the latest in the low bits) and
-// the state the episode ended in -- the values the update would otherwise read back from the trajectory it has just written.
-struct Hand {
-    unsigned long long acts, relq;
-    float reward;
-    int final_rel;
-};
-constexpr int kHandPairs = 4;
+// One lane per thread.  The kernel spends 59 % of a resident wave's time on s_waitcnt with the SIMDs' wave slots full (41 VGPRs), so L
+// independent chains per thread looked like the lever -- measured on configs[1] / configs[3]: L = 1 27.0 / 61.8 us, L = 2 28.2 / 62.4,
+// L = 4 36.8 / 80.3.  It is not the number of lanes in flight that bounds it.
 
 // Distinct trajectories of a work item (k_bucket_play_learn).  A state has exactly one parent entry (ids are DFS pre-order), so the state a
 // lane was last alive in, together with the outcome it drew there -- (row action, column action, chance) into the absorbing state, or
@@ -1512,7 +1428,7 @@ __device__ __forceinline__ bool leaf_crowded(const LeafCount &lc, int bucket) {
            lc.bucket_col0[bucket + 1] - lc.bucket_col0[bucket] <= kLeafHist;
 }
 
-template <int A, typename REL, int L, bool DISTINCT = false, bool HIST = false>
+template <int A, typename REL, bool DISTINCT = false, bool HIST = false>
 __device__ __forceinline__ void rollout_items_body(const Trans *__restrict__ trans, int C, int64_t S, int64_t B, int T_cap,
                                                                    const float *__restrict__ policy_tab, int64_t tab_stride, int vec4,
                                                                    uint64_t seed, const rnad_step_params_t *__restrict__ sp, int64_t lane0,
@@ -1524,13 +1440,13 @@ __device__ __forceinline__ void rollout_items_body(const Trans *__restrict__ tra
                                                                    REL *__restrict__ states, int32_t *__restrict__ alive_part,
                                                                    unsigned long long *__restrict__ acts_out,
                                                                    float *__restrict__ reward_out, int32_t *__restrict__ visited,
-                                                                   double *__restrict__ norm_rep = nullptr, Hand *hand = nullptr,
+                                                                   double *__restrict__ norm_rep = nullptr,
                                                                    const Distinct distinct = Distinct{},
                                                                    const int32_t *__restrict__ col_of = nullptr,
                                                                    int32_t *__restrict__ leaf_col = nullptr, const LeafCount lc = LeafCount{}) {
-    constexpr int NT = kThreads / L, NW = NT / 64;
+    constexpr int NT = kThreads, NW = NT / 64;
     __shared__ int32_t leaf_hist[HIST ? kLeafHist : 1];
-    static_assert(NT >= 64 && NT > kCompactSteps, "a wave at least, and a thread per alive counter");
+    static_assert(NT > kCompactSteps, "a thread per alive counter");
     __shared__ int32_t cnt[NW][kMaxSteps + 1];
     // a row per WORKGROUP (the sum over the rows does not care which item it held) -- or, norm_rep given (k_bucket_play_learn: no launch
     // between the rollout and the finish to add the rows up in), atomics into one of kReplicas rows of counts, which k_bucket_finish sums
@@ -1563,171 +1479,117 @@ __device__ __forceinline__ void rollout_items_body(const Trans *__restrict__ tra
         }
     }
     for (int base = 0; base < item.count; base += kThreads) {  // (one pass: an item holds <= chunk = kThreads lanes unless RNAD_BUCKET_CHUNK says otherwise)
-        bool active[L];
-        uint32_t j[L];
-        int32_t lane_local[L];
-        uint64_t lane[L];
-        unsigned long long packed[L];  // the first decisions, drawn by k_bucket_keys: of the bucket (shared) or of this lane
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int k = base + l * NT + (int)threadIdx.x;
-            active[l] = k < item.count;
-            j[l] = (uint32_t)(item.begin + k);
-            lane_local[l] = active[l] ? lane_ids[j[l]] : 0;
-            lane[l] = (uint64_t)(lane0 + lane_local[l]);
-        }
+        const int k = base + (int)threadIdx.x;
+        const bool active = k < item.count;
+        const uint32_t j = (uint32_t)(item.begin + k);
+        const int32_t lane_local = active ? lane_ids[j] : 0;
+        const uint64_t lane = (uint64_t)(lane0 + lane_local);
+        unsigned long long packed;  // the first decisions, drawn by k_bucket_keys: of the bucket (shared) or of this lane
         if (shared) {
             const unsigned long long first = decisions[lane_ids[item.begin]];
-            const unsigned long long uni = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(first >> 32)) << 32) |
-                                           (unsigned int)__builtin_amdgcn_readfirstlane((int)first);
-#pragma unroll
-            for (int l = 0; l < L; ++l) packed[l] = uni;
+            packed = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(first >> 32)) << 32) |
+                     (unsigned int)__builtin_amdgcn_readfirstlane((int)first);
         } else {
-#pragma unroll
-            for (int l = 0; l < L; ++l) packed[l] = active[l] ? decisions[lane_local[l]] : 0ull;
+            packed = active ? decisions[lane_local] : 0ull;
         }
-        int state[L], n_packed[L], t_from = 0;
-        unsigned long long relq = 0ull;  // (hand: lane 0 of the thread)
-        int last_key[L];                 // (distinct: the key of the lane's trajectory, -1 while it is in the tree)
-        unsigned long long acts[L];
-        float reward_final[L];
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            n_packed[l] = (int)(packed[l] >> 60);
-            last_key[l] = -1;
-            state[l] = active[l] ? 1 : 0;
-            acts[l] = 0ull;
-            reward_final[l] = 0.0f;
-        }
+        const int n_packed = (int)(packed >> 60);
+        int state = active ? 1 : 0, t_from = 0;
+        int last_key = -1;  // (distinct: the key of the lane's trajectory, -1 while it is in the tree)
+        unsigned long long acts = 0ull;
+        float reward_final = 0.0f;
         if (shared) {  // the transitions above the cut, once for the workgroup: the states are the bucket's path, the actions the first lane's
-            const int n_pre = min(min(n_packed[0], T_cap) & ~1, n_shared - 2);
-            int32_t live_now = 0;
-#pragma unroll
-            for (int l = 0; l < L; ++l) live_now += (int32_t)__popcll(__ballot(active[l]));
+            const int n_pre = min(min(n_packed, T_cap) & ~1, n_shared - 2);
+            const int32_t live_now = (int32_t)__popcll(__ballot(active));
             for (int t = 0; t < n_pre; t += 2) {
                 if ((threadIdx.x & 63) == 0) {
                     cnt[wave][t] += live_now;
                     cnt[wave][t + 1] += live_now;
                 }
-                const int bits0 = (int)(packed[0] >> (6 * t)) & 63, bits1 = (int)(packed[0] >> (6 * (t + 1))) & 63;
+                const int bits0 = (int)(packed >> (6 * t)) & 63, bits1 = (int)(packed >> (6 * (t + 1))) & 63;
                 if (visited && threadIdx.x == 0 && base == 0) {
                     const int at = my_path[t];
                     visited[at] = visited[S + at] = 1;
                 }
-#pragma unroll
-                for (int l = 0; l < L; ++l)
-                    acts[l] |= (unsigned long long)(bits0 & 7) << (3 * t) | (unsigned long long)(bits1 & 7) << (3 * (t + 1));
+                acts |= (unsigned long long)(bits0 & 7) << (3 * t) | (unsigned long long)(bits1 & 7) << (3 * (t + 1));
             }
             t_from = n_pre;
-#pragma unroll
-            for (int l = 0; l < L; ++l) state[l] = active[l] ? my_path[n_pre] : 0;  // (n_pre <= n_path: an upper state of the path, or the group's root)
+            state = active ? my_path[n_pre] : 0;  // (n_pre <= n_path: an upper state of the path, or the group's root)
         }
         for (int t = t_from; t < T_cap; t += 2) {
             const bool two = t + 1 < T_cap;  // (an odd T_cap ends with a row step alone)
-            int32_t live = 0;
-#pragma unroll
-            for (int l = 0; l < L; ++l) live += (int32_t)__popcll(__ballot(state[l] != 0));
+            const int32_t live = (int32_t)__popcll(__ballot(state != 0));
             if ((threadIdx.x & 63) == 0) {
                 cnt[wave][t] += live;
                 if (two) cnt[wave][t + 1] += live;  // the row player's step leaves the state as it is
             }
-            bool go[L], replay0[L], replay1[L];
-            float pol0[L][A], pol1[L][A], u[L][3];
-            // every lane's stores and table requests first, then the draws: the L chains overlap their two dependent latencies
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                go[l] = active[l];
-                if (go[l] && t >= n_shared) {  // (n_shared is even: both steps of the transition, or neither)
-                    const REL r = rel_of<REL>(state[l], lo);
-                    if (hand && l == 0) relq = (relq << 16) | (unsigned long long)r;
-                    *at_bytes<REL>(states, ((uint32_t)t * B32 + j[l]) * (uint32_t)sizeof(REL)) = r;
-                    if (two) *at_bytes<REL>(states, ((uint32_t)(t + 1) * B32 + j[l]) * (uint32_t)sizeof(REL)) = r;
-                }
-                go[l] = go[l] && state[l] != 0;
-                replay0[l] = t < n_packed[l];
-                replay1[l] = t + 1 < n_packed[l];
-                if (go[l]) {
-                    const int64_t row0 = state[l], row1 = S + state[l];
-                    if (visited) {
-                        visited[row0] = 1;  // (every writer stores the same value)
-                        if (two) visited[row1] = 1;
-                    }
-                    if (!replay0[l]) load_policy_row<A>(policy_tab, row0, tab_stride, vec4 != 0, pol0[l]);
-                    if (two && !replay1[l]) load_policy_row<A>(policy_tab, row1, tab_stride, vec4 != 0, pol1[l]);
-                }
+            float pol0[A], pol1[A], u[3];
+            // the stores and table requests first, then the draws
+            if (active && t >= n_shared) {  // (n_shared is even: both steps of the transition, or neither)
+                const REL r = rel_of<REL>(state, lo);
+                *at_bytes<REL>(states, ((uint32_t)t * B32 + j) * (uint32_t)sizeof(REL)) = r;
+                if (two) *at_bytes<REL>(states, ((uint32_t)(t + 1) * B32 + j) * (uint32_t)sizeof(REL)) = r;
             }
-#pragma unroll
-            for (int l = 0; l < L; ++l)
-                if (go[l] && (!replay0[l] || (two && !replay1[l]))) rnad_decision_uniforms(seed, lane[l], (uint32_t)t, u[l]);  // computed while the rows travel
-            int a0[L], a1[L], bits1[L];
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                if (!go[l]) continue;
-                const int bits0 = replay0[l] ? (int)(packed[l] >> (6 * t)) & 63 : 0;
-                bits1[l] = replay1[l] ? (int)(packed[l] >> (6 * (t + 1))) & 63 : 0;
-                a0[l] = replay0[l] ? (bits0 & 7) : pick<A>(pol0[l], u[l][0]);
-                acts[l] |= (unsigned long long)a0[l] << (3 * t);
+            const bool go = active && state != 0;
+            const bool replay0 = t < n_packed, replay1 = t + 1 < n_packed;
+            if (go) {
+                const int64_t row0 = state, row1 = S + state;
+                if (visited) {
+                    visited[row0] = 1;  // (every writer stores the same value)
+                    if (two) visited[row1] = 1;
+                }
+                if (!replay0) load_policy_row<A>(policy_tab, row0, tab_stride, vec4 != 0, pol0);
+                if (two && !replay1) load_policy_row<A>(policy_tab, row1, tab_stride, vec4 != 0, pol1);
+            }
+            if (go && (!replay0 || (two && !replay1))) rnad_decision_uniforms(seed, lane, (uint32_t)t, u);  // computed while the rows travel
+            if (go) {
+                const int bits0 = replay0 ? (int)(packed >> (6 * t)) & 63 : 0;
+                const int bits1 = replay1 ? (int)(packed >> (6 * (t + 1))) & 63 : 0;
+                const int a0 = replay0 ? (bits0 & 7) : pick<A>(pol0, u[0]);
+                acts |= (unsigned long long)a0 << (3 * t);
                 if (two) {
-                    a1[l] = replay1[l] ? (bits1[l] & 7) : pick<A>(pol1[l], u[l][1]);
-                    acts[l] |= (unsigned long long)a1[l] << (3 * (t + 1));
-                }
-            }
-            if (two) {
-#pragma unroll
-                for (int l = 0; l < L; ++l) {
-                    if (!go[l]) continue;
+                    const int a1 = replay1 ? (bits1 & 7) : pick<A>(pol1, u[1]);
+                    acts |= (unsigned long long)a1 << (3 * (t + 1));
                     int next, outcome;
                     float rew;
-                    if (replay1[l]) {
-                        outcome = bits1[l] >> 3;
-                        transition_apply<A>(trans, C, state[l], a0[l], a1[l], outcome, next, rew);
+                    if (replay1) {
+                        outcome = bits1 >> 3;
+                        transition_apply<A>(trans, C, state, a0, a1, outcome, next, rew);
                     } else {
-                        transition_lane<A>(trans, C, state[l], a0[l], a1[l], nullptr, u[l][2], next, rew, &outcome);
+                        transition_lane<A>(trans, C, state, a0, a1, nullptr, u[2], next, rew, &outcome);
                     }
                     if (next == 0) {
-                        reward_final[l] = rew;
-                        if (DISTINCT) last_key[l] = (state[l] - lo) * distinct.codes + (a0[l] * A + a1[l]) * C + outcome;
-                        if (leaf_col)
+                        reward_final = rew;
+                        if (DISTINCT) last_key = (state - lo) * distinct.codes + (a0 * A + a1) * C + outcome;
+                        if (leaf_col) {
                             // leaf paths (rnad_leaf_paths_t): the transition a lane leaves the tree by fixes its whole trajectory (a state has one
                             // parent entry) -- the column of that trajectory, per lane in bucket order; the learner's workgroups count the lanes
                             // of their columns in LDS (a global counter per column took a device-scope atomic per lane: 15 us per 2^20 lanes)
-                        {
-                            const int32_t col = col_of[(((uint32_t)state[l] * A + a0[l]) * A + a1[l]) * C + outcome];
-                            leaf_col[j[l]] = col;
+                            const int32_t col = col_of[(((uint32_t)state * A + a0) * A + a1) * C + outcome];
+                            leaf_col[j] = col;
                             if constexpr (HIST)
                                 if (count_here) atomicAdd(&leaf_hist[col - col0], 1);
                         }
-
                     }
-                    state[l] = next;
+                    state = next;
                 }
             }
         }
-        int32_t live = 0;
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            if (active[l]) {
-                acts_out[j[l]] = acts[l];
-                reward_out[j[l]] = reward_final[l];
-                if (T_cap >= n_shared) *at_bytes<REL>(states, ((uint32_t)T_cap * B32 + j[l]) * (uint32_t)sizeof(REL)) = rel_of<REL>(state[l], lo);
-            }
-            live += (int32_t)__popcll(__ballot(state[l] != 0));
+        if (active) {
+            acts_out[j] = acts;
+            reward_out[j] = reward_final;
+            if (T_cap >= n_shared) *at_bytes<REL>(states, ((uint32_t)T_cap * B32 + j) * (uint32_t)sizeof(REL)) = rel_of<REL>(state, lo);
         }
+        const int32_t live = (int32_t)__popcll(__ballot(state != 0));
         if ((threadIdx.x & 63) == 0) cnt[wave][T_cap] += live;
-        if (DISTINCT) {
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                if (!active[l]) continue;
-                const int key = state[l] != 0 ? (state[l] - lo) * distinct.codes + distinct.codes - 1 : last_key[l];
-                const bool in_table = key >= 0 && key < distinct.keys;
-                if (!in_table || atomicAdd(distinct.count + key, 1) == 0) {  // the first lane with this trajectory lists it
-                    const int at = atomicAdd(distinct.n, 1);
-                    distinct.key[at] = in_table ? key : distinct.keys;
-                    distinct.column[at] = (int32_t)j[l];
-                }
+        if (DISTINCT && active) {
+            const int key = state != 0 ? (state - lo) * distinct.codes + distinct.codes - 1 : last_key;
+            const bool in_table = key >= 0 && key < distinct.keys;
+            if (!in_table || atomicAdd(distinct.count + key, 1) == 0) {  // the first lane with this trajectory lists it
+                const int at = atomicAdd(distinct.n, 1);
+                distinct.key[at] = in_table ? key : distinct.keys;
+                distinct.column[at] = (int32_t)j;
             }
         }
-        if (hand) *hand = Hand{acts[0], relq, reward_final[0], active[0] ? (int)rel_of<REL>(state[0], lo) : 0};
     }
     __syncthreads();
     if constexpr (HIST) {
@@ -1756,8 +1618,8 @@ __device__ __forceinline__ void rollout_items_body(const Trans *__restrict__ tra
     }
 }
 
-template <int A, typename REL, int L>
-__global__ __launch_bounds__(kThreads / L) void k_bucket_rollout_items(const Trans *__restrict__ trans, int C, int64_t S, int64_t B, int T_cap,
+template <int A, typename REL>
+__global__ __launch_bounds__(kThreads) void k_bucket_rollout_items(const Trans *__restrict__ trans, int C, int64_t S, int64_t B, int T_cap,
                                                                    const float *__restrict__ policy_tab, int64_t tab_stride, int vec4,
                                                                    uint64_t seed, const rnad_step_params_t *__restrict__ sp, int64_t lane0,
                                                                    const int32_t *__restrict__ lane_ids,
@@ -1768,7 +1630,7 @@ __global__ __launch_bounds__(kThreads / L) void k_bucket_rollout_items(const Tra
                                                                    REL *__restrict__ states, int32_t *__restrict__ alive_part,
                                                                    unsigned long long *__restrict__ acts_out,
                                                                    float *__restrict__ reward_out, int32_t *__restrict__ visited) {
-    rollout_items_body<A, REL, L>(trans, C, S, B, T_cap, policy_tab, tab_stride, vec4, seed, sp, lane0, lane_ids, decisions, items, n_items,
+    rollout_items_body<A, REL>(trans, C, S, B, T_cap, policy_tab, tab_stride, vec4, seed, sp, lane0, lane_ids, decisions, items, n_items,
                                   bucket_path, bucket_lo, path_states, path_stride, n_groups, states, alive_part, acts_out, reward_out, visited);
 }
 
@@ -2171,7 +2033,7 @@ __device__ __forceinline__ void fast_slot(const float *__restrict__ f, const flo
 //
 // Two kernels share the layout and the epilogue (learn_epilogue):
 //   k_bucket_learn<A>            the DENSE trajectory (indices, actions, rewards, acting policy per slot; off-policy batches too)
-//   k_bucket_learn_c<A, REL, L>  the COMPACT trajectory of k_bucket_rollout_items, on-policy (below)
+//   k_bucket_learn_c<A, REL, LOSSES, WEIGHTED>  the COMPACT trajectory of k_bucket_rollout_items, on-policy (below)
 template <int A>
 constexpr int kTabStride = (A + 1) | 1;
 
@@ -2386,14 +2248,6 @@ __global__ __launch_bounds__(kThreads) void k_bucket_learn(int T, int64_t B, int
 //      the r03 kernel, is out of the picture), the gate bits are scalar, and only the carries, the action selects and the addends are
 //      vector work.  Every active lane is valid here (it reached the group).
 // All offsets are 32-bit off scalar bases (tables < 4 GB: the 64-bit address arithmetic was ~10 % of the r03 kernel's VALU work).
-#ifndef RNAD_PHASE2_VMEM
-#define RNAD_PHASE2_VMEM 0
-#endif
-#ifdef RNAD_LEARN_WAVES
-#define RNAD_LEARN_ATTR __attribute__((amdgpu_waves_per_eu(RNAD_LEARN_WAVES, RNAD_LEARN_WAVES)))
-#else
-#define RNAD_LEARN_ATTR
-#endif
 template <int A, typename REL, bool LOSSES, bool DISTINCT = false, bool WEIGHTED = false>
 __device__ __forceinline__ void learn_c_body(int T, int64_t B, int64_t S, int sub_rows, int path_words, int n_groups, int up_stride,
                                                              const Item *__restrict__ items, const int32_t *__restrict__ n_items,
@@ -2406,7 +2260,7 @@ __device__ __forceinline__ void learn_c_body(int T, int64_t B, int64_t S, int su
                                                              unsigned long long *__restrict__ rep, double *__restrict__ losses_raw,
                                                              int32_t *__restrict__ overflow, const int32_t *__restrict__ alive_part,
                                                              int alive_blocks, int T1, int32_t *__restrict__ alive,
-                                                             double *__restrict__ norm_out, const Hand *hand = nullptr,
+                                                             double *__restrict__ norm_out,
                                                              const Distinct distinct = Distinct{}, const int32_t *__restrict__ leaf_col = nullptr,
                                                              const int32_t *__restrict__ lane_start = nullptr,
                                                              const int32_t *__restrict__ lane_total = nullptr, const LeafCount lc = LeafCount{}) {
@@ -2474,20 +2328,10 @@ __device__ __forceinline__ void learn_c_body(int T, int64_t B, int64_t S, int su
             if (__ballot(active) == 0ull) continue;  // (a wave whose columns are all empty: nothing to add, no barrier inside the loop)
         }
         Carry cy[2];
-        // (k_bucket_play_learn, an item played in one pass: this thread's own values arrive in registers)
-        const bool handed = hand != nullptr && item.count <= kThreads;
-        const unsigned long long acts = handed ? hand->acts : active ? acts_[j] : 0ull;
-        const float reward_final = handed ? hand->reward : active ? reward_[j] : 0.0f;
-        const int last_pair = (T - 1) >> 1;
+        const unsigned long long acts = active ? acts_[j] : 0ull;
+        const float reward_final = active ? reward_[j] : 0.0f;
+        auto state_at = [&](int t) { return (int)*at_bytes<REL>(states, ((uint32_t)t * B32 + j) * (uint32_t)sizeof(REL)); };
         // the state the last step of the window led to (rewards *= (indices == 0), episode.py:120-121: the step into state 0 pays)
-        auto state_at = [&](int t) {
-            if (handed) {
-                if (t == T) return hand->final_rel;
-                const int k = last_pair - (t >> 1);
-                if (k < kHandPairs) return (int)((hand->relq >> (16 * k)) & 0xffffull);
-            }
-            return (int)*at_bytes<REL>(states, ((uint32_t)t * B32 + j) * (uint32_t)sizeof(REL));
-        };
         bool after_zero = active && (T < n_shared ? false : state_at(T) == 0);
         // ------------------------------------------------------------------ phase 1: per-lane states below the cut
         if (t_low < T && !(RNAD_ABLATE & 8)) {
@@ -2550,19 +2394,9 @@ __device__ __forceinline__ void learn_c_body(int T, int64_t B, int64_t S, int su
         if (active && t_low > 0 && !(RNAD_ABLATE & 16)) {
             auto row_of = [&](int t, int state) { return (uint32_t)(t & 1) * S32 + (uint32_t)state; };
             auto load_rec = [&](uint32_t row, float (&f)[FS], float (&lg)[A]) {
-#if RNAD_PHASE2_VMEM  // experiment: the same record through the vector path (every lane the same address)
-                asm volatile("" : "+v"(row));
-                const float4 *r4p = at_bytes<float4>(rec_, row * (uint32_t)(FS * sizeof(float)));
-#pragma unroll
-                for (int u = 0; u < FS / 4; ++u) {
-                    const float4 r4 = r4p[u];
-                    f[4 * u] = r4.x; f[4 * u + 1] = r4.y; f[4 * u + 2] = r4.z; f[4 * u + 3] = r4.w;
-                }
-#else
                 const float *rp = at_bytes<float>(rec_, row * (uint32_t)(FS * sizeof(float)));
 #pragma unroll
                 for (int u = 0; u < FS; ++u) f[u] = rp[u];
-#endif
                 if (LOSSES) {
                     const float *lp = at_bytes<float>(logit_, row * (uint32_t)(RS * sizeof(float)));
 #pragma unroll
@@ -2608,7 +2442,7 @@ __device__ __forceinline__ void learn_c_body(int T, int64_t B, int64_t S, int su
 }
 
 template <int A, typename REL, bool LOSSES, bool WEIGHTED = false>
-__global__ __launch_bounds__(kThreads) RNAD_LEARN_ATTR void k_bucket_learn_c(int T, int64_t B, int64_t S, int sub_rows, int path_words, int n_groups, int up_stride,
+__global__ __launch_bounds__(kThreads) void k_bucket_learn_c(int T, int64_t B, int64_t S, int sub_rows, int path_words, int n_groups, int up_stride,
                                                              const Item *__restrict__ items, const int32_t *__restrict__ n_items,
                                                              const int32_t *__restrict__ bucket_of, const int32_t *__restrict__ bucket_lo,
                                                              const int32_t *__restrict__ bucket_path, const int32_t *__restrict__ path_states,
@@ -2624,7 +2458,7 @@ __global__ __launch_bounds__(kThreads) RNAD_LEARN_ATTR void k_bucket_learn_c(int
                                                              LeafCount lc) {
     learn_c_body<A, REL, LOSSES, false, WEIGHTED>(T, B, S, sub_rows, path_words, n_groups, up_stride, items, n_items, bucket_of, bucket_lo, bucket_path,
                                                   path_states, path_stride, states, rec_, acts_, reward_, logit_, hp, fx, acc, rep, losses_raw, overflow,
-                                                  alive_part, alive_blocks, T1, alive, norm_out, nullptr, Distinct{}, leaf_col, lane_start, lane_total, lc);
+                                                  alive_part, alive_blocks, T1, alive, norm_out, Distinct{}, leaf_col, lane_start, lane_total, lc);
 }
 
 // The rollout half of the leaf-path step (rnad_leaf_paths_t): k_bucket_rollout_items with the alive counts and normalisers left in the
@@ -2642,35 +2476,24 @@ __global__ __launch_bounds__(kThreads) void k_bucket_play_count(const Trans *__r
                                                                 int32_t *__restrict__ alive_rep, double *__restrict__ norm_rep,
                                                                 unsigned long long *__restrict__ acts_out, float *__restrict__ reward_out,
                                                                 const int32_t *__restrict__ col_of, int32_t *__restrict__ leaf_col, LeafCount lc) {
-    rollout_items_body<A, REL, 1, false, true>(trans, C, S, B, T_cap, policy_tab, tab_stride, vec4, seed, sp, lane0, lane_ids, decisions, items, n_items,
+    rollout_items_body<A, REL, false, true>(trans, C, S, B, T_cap, policy_tab, tab_stride, vec4, seed, sp, lane0, lane_ids, decisions, items, n_items,
                                   bucket_path, bucket_lo, path_states, path_stride, n_groups, states, alive_rep, acts_out, reward_out, nullptr,
-                                  norm_rep, nullptr, Distinct{}, col_of, leaf_col, lc);
+                                  norm_rep, Distinct{}, col_of, leaf_col, lc);
 }
 
 // Rollout and learner of a work item in ONE launch (r04): the workgroup that played the item's lanes runs their update right away --
 // thread k reads back what it played itself (packed actions, reward, states of lane item.begin + k: its own stores, program order, no
-// fence; RNAD_HANDOVER=1 keeps them in registers instead -- struct Hand --, which costs the sixth wave per SIMD and more than it saves),
+// fence; handing them over in registers instead was measured in r04: it costs the sixth wave per SIMD and more than it saves, below),
 // so the trajectory is the one k_bucket_rollout_items leaves and the sums are the ones k_bucket_learn_c adds up, bit for bit.  What it buys is
 // a launch floor and the overlap of the rollout's gather latency with the learner's arithmetic across the workgroups of a CU
 // (tools/micro/overlap_probe.py: the two kernels side by side on two streams take 80 us where back to back they take 95).
 // The alive counts and the normalisers go, with atomics, into one of kReplicas rows each (alive_rep, norm_rep: behind the learner's
 // accumulators, zero between updates); k_bucket_finish -- or k_bucket_alive_rep, when the finish is the caller's -- adds the rows up,
 // hands alive[] / norm[] out and clears them.
-#ifndef RNAD_HANDOVER
-#define RNAD_HANDOVER 0
-#endif
-// (build switch: waves per SIMD the compiler must leave room for.  On its own it takes 77 VGPRs (DISTINCT: 79) -- six waves; with
-// RNAD_HANDOVER it takes 85, runs at five and loses 7 %: 73.8 -> 79.1 us)
-#ifndef RNAD_PLAY_LEARN_WAVES
-#define RNAD_PLAY_LEARN_WAVES 0
-#endif
-#if RNAD_PLAY_LEARN_WAVES > 0
-#define RNAD_PLAY_LEARN_ATTR __attribute__((amdgpu_waves_per_eu(RNAD_PLAY_LEARN_WAVES, RNAD_PLAY_LEARN_WAVES)))
-#else
-#define RNAD_PLAY_LEARN_ATTR
-#endif
+// (The kernel takes 77 VGPRs (DISTINCT: 79) -- six waves per SIMD; with the hand-over in registers it took 85, ran at five and lost 7 %:
+// 73.8 -> 79.1 us.)
 template <int A, typename REL, bool DISTINCT>
-__global__ __launch_bounds__(kThreads) RNAD_PLAY_LEARN_ATTR void k_bucket_play_learn(
+__global__ __launch_bounds__(kThreads) void k_bucket_play_learn(
     const Trans *__restrict__ trans, int C, int64_t S, int64_t B, int T_cap, const float *__restrict__ policy_tab, int64_t tab_stride, int vec4,
     uint64_t seed, const rnad_step_params_t *__restrict__ sp, int64_t lane0, const int32_t *__restrict__ lane_ids,
     const unsigned long long *__restrict__ decisions, const Item *__restrict__ items, const int32_t *__restrict__ n_items,
@@ -2693,13 +2516,11 @@ __global__ __launch_bounds__(kThreads) RNAD_PLAY_LEARN_ATTR void k_bucket_play_l
         for (int i = threadIdx.x; i < distinct_keys + 2; i += kThreads) dd.count[i] = i == distinct_keys ? 1 : 0;
         __syncthreads();
     }
-    Hand hand{0ull, 0ull, 0.0f, 0};
-    rollout_items_body<A, REL, 1, DISTINCT>(trans, C, S, B, T_cap, policy_tab, tab_stride, vec4, seed, sp, lane0, lane_ids, decisions, items, n_items,
-                                  bucket_path, bucket_lo, path_states, path_stride, n_groups, states, alive_rep, acts, reward, nullptr, norm_rep,
-                                  RNAD_HANDOVER ? &hand : nullptr, dd);
+    rollout_items_body<A, REL, DISTINCT>(trans, C, S, B, T_cap, policy_tab, tab_stride, vec4, seed, sp, lane0, lane_ids, decisions, items, n_items,
+                                  bucket_path, bucket_lo, path_states, path_stride, n_groups, states, alive_rep, acts, reward, nullptr, norm_rep, dd);
     learn_c_body<A, REL, false, DISTINCT>(T_cap, B, S, sub_rows, path_words, n_groups, up_stride, items, n_items, bucket_of, bucket_lo, bucket_path,
                                 path_states, path_stride, states, rec_, acts, reward, nullptr, hp, fx, acc, rep, nullptr, overflow, nullptr, 0,
-                                T_cap + 1, nullptr, nullptr, RNAD_HANDOVER ? &hand : nullptr, dd);
+                                T_cap + 1, nullptr, nullptr, dd);
 }
 
 // acc -> fp32 tables, normalised: dlogit_tab[P * S + s] = w_n * (G_l / N_P), dv_tab likewise with w_v (learn/vtrace.py:374,389;
@@ -3298,13 +3119,13 @@ struct RolloutCall {
 
     template <int A, int TILE>
     int keys_lds(size_t lds, const KeysExpand &ex) const {
-        return launch_lds(k_bucket_keys_lds<A, kPlayLds, TILE>, dim3(p.sort_blocks), dim3(kSortThreads), lds, stream, (const UpperWalk *)cut.upper_walk,
+        return launch_lds(k_bucket_keys_lds<A, TILE>, dim3(p.sort_blocks), dim3(kSortThreads), lds, stream, (const UpperWalk *)cut.upper_walk,
                           (const int32_t *)cut.upper_list, cut.n_upper, cut.n_buckets, tree->C, S, B, n_steps, policy_tab, policy_stride,
                           (int)cut.host_bucket_of[1], cut.n_groups, seed, device_params, lane0, s.keys, s.decisions, s.hist, rq.sort.norm, stage, ex);
     }
     template <int A, int TILE>
     int keys_hybrid(size_t lds) const {
-        return launch_lds(k_bucket_keys_hybrid<A, kPlayLds, TILE>, dim3(p.sort_blocks), dim3(kSortThreads), lds, stream, (const UpperWalk *)cut.upper_walk,
+        return launch_lds(k_bucket_keys_hybrid<A, TILE>, dim3(p.sort_blocks), dim3(kSortThreads), lds, stream, (const UpperWalk *)cut.upper_walk,
                           (const int32_t *)cut.upper_list, (const int32_t *)cut.hot_list, (const int32_t *)cut.hot_of, cut.n_hot, cut.n_upper,
                           tree->trans, (const int32_t *)cut.bucket_of, tree->C, S, B, n_steps, policy_tab, policy_stride, vec4,
                           (int)cut.host_bucket_of[1], cut.n_groups, seed, device_params, lane0, s.keys, s.decisions, rq.sort.norm, stage,
@@ -3326,7 +3147,7 @@ struct RolloutCall {
     }
     template <int A, class REL>
     void rollout_items() const {
-        hipLaunchKernelGGL((k_bucket_rollout_items<A, REL, kRolloutLanes>), dim3((unsigned)p.max_items), dim3(kThreads / kRolloutLanes), 0, stream,
+        hipLaunchKernelGGL((k_bucket_rollout_items<A, REL>), dim3((unsigned)p.max_items), dim3(kThreads), 0, stream,
                            tree->trans, tree->C, S, B, rq.T_cap, policy_tab, policy_stride, vec4, seed, device_params, lane0,
                            (const int32_t *)rq.sort.lane_ids, (const unsigned long long *)s.decisions, (const Item *)rq.sort.items,
                            (const int32_t *)rq.sort.n_items, (const int32_t *)cut.bucket_path, (const int32_t *)cut.bucket_lo,

@@ -16,14 +16,16 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "r-nad_amd"))
 import isa_hist  # noqa: E402
 
+# (source, kernel, key in the JSON: the name bench.py looks the kernel up under -- for the kernels that played a build-time number of
+# lanes per thread, the template list they had then)
 KERNELS = [
-    ("bucket.hip", "k_bucket_learn_c<3, unsigned char, false, false>"),
-    ("bucket.hip", "k_bucket_learn_c<5, unsigned char, false, false>"),
-    ("bucket.hip", "k_bucket_play_learn<3, unsigned char, false>"),
-    ("bucket.hip", "k_bucket_rollout_items<3, unsigned char, 1>"),
-    ("bucket.hip", "k_bucket_rollout_items<5, unsigned char, 1>"),
-    ("bucket.hip", "k_bucket_keys_lds<3, 1, 4096>"),
-    ("bucket.hip", "k_bucket_keys_hybrid<5, 1, 4096>"),
+    ("bucket.hip", "k_bucket_learn_c<3, unsigned char, false, false>", None),
+    ("bucket.hip", "k_bucket_learn_c<5, unsigned char, false, false>", None),
+    ("bucket.hip", "k_bucket_play_learn<3, unsigned char, false>", None),
+    ("bucket.hip", "k_bucket_rollout_items<3, unsigned char>", "k_bucket_rollout_items<3, unsigned char, 1>"),
+    ("bucket.hip", "k_bucket_rollout_items<5, unsigned char>", "k_bucket_rollout_items<5, unsigned char, 1>"),
+    ("bucket.hip", "k_bucket_keys_lds<3, 4096>", "k_bucket_keys_lds<3, 1, 4096>"),
+    ("bucket.hip", "k_bucket_keys_hybrid<5, 4096>", "k_bucket_keys_hybrid<5, 1, 4096>"),
 ]
 
 
@@ -36,7 +38,7 @@ def main():
     out = {"source_hash": rnad_hip.source_hash(), "how": "tools/isa_hist.py --loop (hipcc -S --offload-arch=gfx950, the Makefile's flags): "
            "share of each issue class among the VALU instructions inside the kernel's loops", "kernels": {}}
     asm_cache = {}
-    for src, pattern in KERNELS:
+    for src, pattern, key in KERNELS:
         path = os.path.join(ROOT, "r-nad_amd", "csrc", src)
         if path not in asm_cache:
             asm = isa_hist.compile_asm(path)
@@ -47,7 +49,7 @@ def main():
         body, meta = kernels[name]
         hist, _ = isa_hist.histogram(body, True)
         valu = sum(hist[c] for c in isa_hist.VALU_CLASSES)
-        out["kernels"][pattern] = {"valu": valu, "share": {c: hist[c] / valu for c in isa_hist.VALU_CLASSES if hist[c]}, "resources": meta,
+        out["kernels"][key or pattern] = {"valu": valu, "share": {c: hist[c] / valu for c in isa_hist.VALU_CLASSES if hist[c]}, "resources": meta,
                                    "other": {c: hist[c] for c in ("salu", "smem", "vmem", "lds", "wait", "branch") if hist[c]}}
     with open(os.path.join(ROOT, "profiles", "r06_isa_mix.json"), "w") as f:
         json.dump(out, f, indent=1)
