@@ -112,6 +112,12 @@ int rnad_mlp_forward(int64_t N, int A, int W, const float *packed, const void *o
  * target and two regularisation nets (learn/rnad.py:373-380) on the 2S observations of the tree. */
 int rnad_mlp_forward_multi(int n_nets, int64_t N, int A, int W, const float *const *packed, const void *obs, int obs_half,
                            float *const *logits, float *const *value, void *stream);
+/* The launch the forward entry points (fold != 0: rnad_mlp_forward_fold and the fold actor) give N samples, or a row list of capacity N,
+ * and n_nets nets on a device of `cus` compute units; host arithmetic only, no device is touched, and the launch itself is computed by the
+ * same code.  out [4]: bytes of the weight image in LDS, resident workgroups per CU the grid is sized for, workgroups per net (the grid
+ * is n_nets times that), the largest number of 64-sample spans any wave walks.  Refuses what the launch refuses: a width that is no
+ * positive multiple of 32, A outside 1..8, the fold with A < 2, an image over 160 KiB. */
+int rnad_mlp_forward_plan(int64_t N, int A, int W, int fold, int n_nets, int cus, int64_t *out);
 int64_t rnad_mlp_backward_workspace(int64_t N, int A, int W);
 int rnad_mlp_backward(int64_t N, int A, int W, const float *packed, const void *obs, int obs_half, const float *dlogits,
                       const float *dvalue, float *g_vw0, float *g_vb0, float *g_vw1, float *g_vb1, float *g_pw0,

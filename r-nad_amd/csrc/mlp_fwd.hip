@@ -281,31 +281,58 @@ extern "C" int rnad_mlp_pack(int A, int W, const float *vw0, const float *vb0, c
     return rnad_mlp_pack_multi(1, A, W, w, out, stream);
 }
 
+// The launch of k_mlp_forward for N samples (or a row list of capacity N) and n_nets nets on a device of `cus` compute units: host
+// arithmetic only, shared by mlp_forward_launch and the rnad_mlp_forward_plan export.
+struct FwdPlan {
+    size_t lds_bytes;   // the weight image every workgroup holds
+    int blocks_per_cu;  // resident workgroups per CU that the grid is sized for
+    int64_t per_net;    // workgroups per net (the grid is n_nets * per_net)
+    int64_t rounds;     // the largest number of 64-sample spans any wave walks
+};
+
+static int mlp_forward_plan(int64_t N, int A, int W, bool fold, int n_nets, int cus, FwdPlan *p) {
+    RNAD_REQUIRE(W >= kTile && W % kTile == 0, "rnad_mlp_forward: width %d must be a positive multiple of %d", W, kTile);
+    RNAD_REQUIRE(A >= 1 && A <= RNAD_MAX_ACTIONS, "rnad_mlp_forward: max_actions %d out of range [1,%d]", A, RNAD_MAX_ACTIONS);
+    RNAD_REQUIRE(N >= 0, "rnad_mlp_forward: negative batch");
+    RNAD_REQUIRE(n_nets >= 1 && n_nets <= 4 && cus >= 1, "rnad_mlp_forward: 1..4 nets on at least one compute unit");
+    RNAD_REQUIRE(!fold || A >= 2, "rnad_mlp_forward_fold: the legal fold needs at least two actions");
+    p->lds_bytes = (size_t)(fold ? mlp_packed_floats_fold(A, W) : mlp_packed_floats(A, W)) * sizeof(float);
+    RNAD_REQUIRE(p->lds_bytes <= 160 * 1024, "rnad_mlp_forward: weights (%zu B) do not fit the 160 KiB LDS (A=%d, width=%d)", p->lds_bytes, A, W);
+    constexpr int kWaves = kFwdThreads / 64;
+    p->blocks_per_cu = std::max(1, std::min(12 / kWaves, (int)(160 * 1024 / p->lds_bytes)));
+    const int64_t n_spans = (N + 2 * kTile - 1) / (2 * kTile);  // a wave iteration covers 64 samples
+    // every net of the launch gets its own full round of workgroups, in one linear grid (a launch per head set cost ~6 us more at
+    // the tabular update's 132 862 rows; one persistent round split evenly / by cost over the nets: 59.8 / 64.5 us instead of 53;
+    // workgroups whose waves split the hidden tiles of one span: no faster there and 46 % slower at 1.9 M rows)
+    p->per_net = std::max<int64_t>(1, std::min<int64_t>((n_spans + kWaves - 1) / kWaves, (int64_t)cus * p->blocks_per_cu));
+    p->rounds = (n_spans + p->per_net * kWaves - 1) / (p->per_net * kWaves);
+    return 0;
+}
+
+extern "C" int rnad_mlp_forward_plan(int64_t N, int A, int W, int fold, int n_nets, int cus, int64_t *out) {
+    RNAD_REQUIRE(out, "rnad_mlp_forward_plan: null argument");
+    FwdPlan p{};
+    if (int rc = mlp_forward_plan(N, A, W, fold != 0, n_nets, cus, &p)) return rc;
+    out[0] = (int64_t)p.lds_bytes; out[1] = p.blocks_per_cu; out[2] = p.per_net; out[3] = p.rounds;
+    return 0;
+}
+
 static int mlp_forward_launch(int64_t N, const int32_t *rows, const int64_t *n_rows, int A, int W, int n_nets, const NetSet &nets,
                               const void *obs, int obs_half, void *stream_, bool fold = false) {
     RNAD_REQUIRE(obs && n_nets >= 1 && n_nets <= 4, "rnad_mlp_forward: null argument");
     for (int i = 0; i < n_nets; ++i)
         RNAD_REQUIRE(nets.packed[i] && (nets.logits[i] || nets.value[i]), "rnad_mlp_forward: null argument (net %d)", i);
-    RNAD_REQUIRE(W >= kTile && W % kTile == 0, "rnad_mlp_forward: width %d must be a positive multiple of %d", W, kTile);
-    RNAD_REQUIRE(N >= 0, "rnad_mlp_forward: negative batch");
-    if (N == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
-    RNAD_REQUIRE(!fold || A >= 2, "rnad_mlp_forward_fold: the legal fold needs at least two actions");
-    const size_t lds_bytes = (size_t)(fold ? mlp_packed_floats_fold(A, W) : mlp_packed_floats(A, W)) * sizeof(float);
-    RNAD_REQUIRE(lds_bytes <= 160 * 1024, "rnad_mlp_forward: weights (%zu B) do not fit the 160 KiB LDS (A=%d, width=%d)", lds_bytes, A, W);
     int dev = 0, cus = 256;
     RNAD_HIP_OK(hipGetDevice(&dev));
     RNAD_HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    constexpr int kWaves = kFwdThreads / 64;
-    const int blocks_per_cu = std::max(1, std::min(12 / kWaves, (int)(160 * 1024 / lds_bytes)));
-    const int64_t n_spans = (N + 2 * kTile - 1) / (2 * kTile);  // a wave iteration covers 64 samples
-    // every net of the launch gets its own full round of workgroups, in one linear grid (a launch per head set cost ~6 us more at
-    // the tabular update's 132 862 rows; one persistent round split evenly / by cost over the nets: 59.8 / 64.5 us instead of 53;
-    // workgroups whose waves split the hidden tiles of one span: no faster there and 46 % slower at 1.9 M rows)
-    const int64_t per_net = std::max<int64_t>(1, std::min<int64_t>((n_spans + kWaves - 1) / kWaves, (int64_t)cus * blocks_per_cu));
+    FwdPlan plan{};
+    if (int rc = mlp_forward_plan(N, A, W, fold, n_nets, cus, &plan)) return rc;  // (the refusals: shape, fold, LDS)
+    if (N == 0) return 0;
+    const size_t lds_bytes = plan.lds_bytes;
     NetSet launch = nets;
     launch.first_block[0] = 0;
-    for (int i = 0; i < 4; ++i) launch.first_block[i + 1] = i < n_nets ? launch.first_block[i] + (int)per_net : 0x7fffffff;
+    for (int i = 0; i < 4; ++i) launch.first_block[i + 1] = i < n_nets ? launch.first_block[i] + (int)plan.per_net : 0x7fffffff;
     const unsigned grid = (unsigned)launch.first_block[n_nets];
     // only the heads that are wanted are computed: the kernel is instantiated for their union over the nets of the launch
     int heads = 0;

@@ -480,23 +480,38 @@ def mlp_forward_actor(tree, packed, W, obs, logits, policy_rows, rows=None, fold
                                         int(half), _dp(logits, F32, "logits"), _dp(policy_rows, F32, "policy_rows"), _stream()))
 
 
-def mlp_forward_multi(packed_list, W, obs, A, wants, fold=False, live=None, zero_rest=True):
+def mlp_forward_plan(N, A, W, fold=False, n_nets=1, cus=256):
+    """The launch the forward gives N samples and n_nets nets on a device of `cus` compute units (rnad_mlp_forward_plan: host arithmetic,
+    no device): lds_bytes, blocks_per_cu, per_net (workgroups per net), rounds (the most 64-sample spans any wave walks)."""
+    import types
+
+    out = (C.c_int64 * 4)()
+    _check(lib().rnad_mlp_forward_plan(C.c_int64(N), A, W, int(bool(fold)), n_nets, cus, out))
+    return types.SimpleNamespace(lds_bytes=out[0], blocks_per_cu=out[1], per_net=out[2], rounds=out[3])
+
+
+def mlp_forward_multi(packed_list, W, obs, A, wants, fold=False, live=None, zero_rest=True, out=None):
     """Several nets of one shape on the same inputs in ONE launch (rnad_mlp_forward_multi).  packed_list: their weight images;
     wants: per net (want_logits, want_value).  Returns a list of (logits [N, A] or None, value [N, 1] or None).
-    live (FOLD kernels only): a row list -- only those rows are evaluated (the others: zeros, or uninitialised with zero_rest=False)."""
+    live (FOLD kernels only): a row list -- only those rows are evaluated (the others: zeros, or uninitialised with zero_rest=False).
+    out: per net (logits, value), existing tables to write into (None: that head is not wanted); `wants` is then taken from it."""
     fold = _fold_checked(fold, obs, "mlp_forward_multi")
     n = len(packed_list)
-    assert 1 <= n <= 4 and len(wants) == n
+    assert 1 <= n <= 4 and (out is not None or len(wants) == n)
     N = obs.numel() // (2 * A * A)
     half = obs.dtype == F16
     assert live is None or (fold and live.N == N), "a row list goes with the FOLD kernels"
     alloc = torch.zeros if (live is not None and zero_rest) else torch.empty
-    outs = [(alloc((N, A), dtype=F32, device=obs.device) if wl else None,
-             alloc((N, 1), dtype=F32, device=obs.device) if wv else None) for wl, wv in wants]
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    if out is not None:
+        outs = [tuple(o) for o in out]
+        assert len(outs) == n and all((lg is None or lg.shape == (N, A)) and (v is None or v.shape == (N, 1)) for lg, v in outs)
+    else:
+        outs = [(alloc((N, A), dtype=F32, device=obs.device) if wl else None,
+                 alloc((N, 1), dtype=F32, device=obs.device) if wv else None) for wl, wv in wants]
+    ptr = lambda t, name: _dp(t, F32, name).value if t is not None else None  # noqa: E731
     P = (C.c_void_p * n)(*[_dp(p, F32, "packed").value for p in packed_list])
-    L = (C.c_void_p * n)(*[ptr(o[0]) for o in outs])
-    V = (C.c_void_p * n)(*[ptr(o[1]) for o in outs])
+    L = (C.c_void_p * n)(*[ptr(o[0], "logits") for o in outs])
+    V = (C.c_void_p * n)(*[ptr(o[1], "value") for o in outs])
     if fold:
         _check(lib().rnad_mlp_forward_fold(n, C.c_int64(N), *_row_list(live), A, W, P, _dp(obs, F16 if half else F32, "obs"), int(half), L, V,
                                            _stream()))

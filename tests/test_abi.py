@@ -47,6 +47,7 @@ def test_binding_takes_every_prototype_from_the_header():
     assert list(lib.rnad_sample.argtypes) == [i64, i32, ptr, ptr, u64, i64, i32, i32, ptr, ptr]
     assert list(lib.rnad_clip_grad_norm.argtypes) == [i64, ptr, f32, ptr, ptr]
     assert list(lib.rnad_mlp_backward_plan.argtypes) == [i64, i32, i32, i32, ptr] and lib.rnad_mlp_backward_plan.restype == i32
+    assert list(lib.rnad_mlp_forward_plan.argtypes) == [i64, i32, i32, i32, i32, i32, ptr] and lib.rnad_mlp_forward_plan.restype == i32
     assert lib.rnad_tree_info.restype == i64 and lib.rnad_last_error.restype == ctypes.c_char_p and lib.rnad_tree_destroy.restype is None
     # full-width conversion of a bare Python int (no c_int64 wrapper at the call site)
     assert lib.rnad_compact_workspace(2**40) == 2**40 // 2048 + 1
