@@ -785,6 +785,29 @@ int rnad_nashconv(const rnad_tree_t *tree, const float *joint_policy, const floa
 int rnad_observe_all(const rnad_tree_t *tree, float *obs_row, float *obs_col, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cross-play  --  no counterpart in the reference, which can only sample games of one net against
+ * itself (Episodes.generate, environment/episode.py:175-230).  It sits next to the bottom-up half of get_nashconv
+ * (util/metric.py:134-175) and walks the same tables: the exact expected payoff of "policy i plays
+ * the rows, policy j plays the columns" for every pair of n policies, in one sweep of the tree.
+ *   V[0, i, j] = 0
+ *   V[s, i, j] = sum_{r,c} J_i[s, r] * J_j[s, A + c] * sum_t chance[s,t,r,c] * (next == 0 ? value : V[next, i, j])
+ *   U[i, j]    = V[1, i, j]      (the row player's payoff; the column player's is -U)
+ * Entries with chance <= 0 are skipped.  The orientation is that of metric.py:169-170, not the
+ * pi_col[r] * pi_row[c] product of the reach sweep (:130-132).
+ * policies f32 [S][n][2A] (device): table k of a state is the joint_policy row of player k (row
+ * player's policy in [:A], column player's in [A:]).  values f32 [S][n][n] (device) is workspace and
+ * result: every row is written -- state 0 and states no chance > 0 path reaches with zeros -- and
+ * nothing else is allocated or cleared, so the call can be captured in a hipGraph.  One launch per
+ * level, bottom-up, on `stream`; no atomics and a fixed summation order: the same inputs give the
+ * same bits.  The transition table is read once per 64 pairs, not once per pair.
+ * rnad_cross_play_size (host only): floats of `values` = S * n * n; -1 unless S >= 2 and
+ * 1 <= n <= RNAD_CROSS_PLAY_MAX.
+ * ---------------------------------------------------------------------------------------------- */
+#define RNAD_CROSS_PLAY_MAX 32
+int64_t rnad_cross_play_size(int64_t S, int n);
+int rnad_cross_play(const rnad_tree_t *tree, int n, const float *policies, float *values, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Native tree generator (HOST code)  --  environment/tree.py:164-366 (generate, _transition_probs,
  * _solve) for trees too large for the Python recursion (66 431 states take > 100 s there).
  * Regular shape only: every state has A x A legal actions and depth_bound - 1 below it; chance

@@ -432,6 +432,20 @@ class RNaD:
             logging.info("  depth %s: %s", depth, mean)
         return (data.row_best[1] + data.col_best[1]).item()
 
+    def cross_play(self, *others) -> "metric.CrossPlay":
+        """Exact payoff matrix of this trainer's target net (player 0) against the target nets of `others`, trainers over the same tree
+        (the `for eta in ...` runs of main.py:55-81): util.metric.cross_play, no sampled games.  Another tree is refused, by its hash."""
+        for k, other in enumerate(others):
+            if other.tree is not self.tree and (other.tree.hash != self.tree.hash
+                                                or other.tree.value_tensor.shape != self.tree.value_tensor.shape):
+                raise ValueError(f"cross_play: trainer {k + 1} ('{other.directory_name}') plays another tree "
+                                 f"(hash {other.tree.hash} != {self.tree.hash})")
+            if other.net_target is None:
+                raise ValueError(f"cross_play: trainer {k + 1} ('{other.directory_name}') is not initialised")
+        if self.net_target is None:
+            raise ValueError("cross_play: this trainer is not initialised")
+        return metric.cross_play(self.tree, [self.net_target] + [other.net_target for other in others])
+
     def _grad_bucket(self, weights):
         """One flat fp32 buffer holding the learner's gradients back to back (the RCCL bucket) and per-tensor views of it."""
         n = sum(w.numel() for w in weights)

@@ -1896,6 +1896,35 @@ def nashconv(tree, joint_policy, root_policy, state_index, reach, row_best, col_
                                _dp(depth_out, I32, "depth"), _stream()))
 
 
+CROSS_PLAY_MAX = 32
+
+
+def cross_play(tree, policies, values=None):
+    """rnad_cross_play: policies f32 [S, n, 2A] (table k of a state = the joint_policy row of player k) -> values f32 [S, n, n], the exact
+    expected payoff of the row player at every state when player i plays the rows and player j the columns; values[1] is the payoff
+    matrix.  values: an existing buffer to fill (every row is written).  Allocates nothing else: capturable."""
+    if not torch.is_tensor(policies) or policies.dim() != 3:
+        raise RnadHipError("cross_play: policies must be a tensor of shape [S, n, 2A]")
+    pp = _dp(policies, F32, "policies")
+    if not isinstance(tree, TreeHandle):
+        raise RnadHipError("cross_play: tree must be a TreeHandle (Tree.handle())")
+    S, n, A2 = policies.shape
+    if S != tree.S or A2 != 2 * tree.A:
+        raise RnadHipError(f"cross_play: policies of shape {tuple(policies.shape)} do not fit a tree of {tree.S} states and {tree.A} actions "
+                           f"(expected [{tree.S}, n, {2 * tree.A}])")
+    if lib().rnad_cross_play_size(S, n) < 0:
+        raise RnadHipError(f"cross_play: {n} policies outside [1, {CROSS_PLAY_MAX}]")
+    if policies.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
+        raise RnadHipError(f"cross_play: policies live on {policies.device}, the tree's tables on {tree.device}")
+    if values is None:
+        values = torch.empty((S, n, n), dtype=F32, device=policies.device)
+    vp = _dp(values, F32, "values")
+    if tuple(values.shape) != (S, n, n) or values.device != policies.device:
+        raise RnadHipError(f"cross_play: values must be [{S}, {n}, {n}] on {policies.device}, got {tuple(values.shape)} on {values.device}")
+    _check(lib().rnad_cross_play(tree.ptr, n, pp, vp, _stream()))
+    return values
+
+
 # --------------------------------------------------------------------------------------- host-side: generator / solver
 def solve_matrix(M, max_actions):
     """tree.py:199-234 for one fp32 matrix (CPU tensor [ra, ca]) -> (solution [2*max_actions], value)."""

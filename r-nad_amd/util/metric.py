@@ -4,8 +4,11 @@
 and methods (`get_nashconv_from_net`, `get_nashconv`, `mean_nashconv_by_depth`).  The reference moves the tree to the
 CPU and recurses in Python with ~20 tiny tensor ops per state (metric.py:84-175); here the whole tree is inferenced
 with two `forward_policy` calls per slice and the best-response values come from rnad_nashconv's two level sweeps.
+
+`cross_play(tree, players)` is an addition without a counterpart in the reference: the exact payoff matrix of n nets or policy
+tables against each other (rnad_cross_play, one bottom-up sweep for all n * n pairs), with each player's NashConv next to it.
 """
-from typing import Dict
+from typing import Dict, NamedTuple
 
 import torch
 
@@ -31,15 +34,7 @@ class NashConvData:
     def get_nashconv_from_net(self, tree, net, inference_batch_size: int = 10**5) -> None:
         """Inference every state for both players, then evaluate.  Observations of all states come from K1 with
         idx = 0..S-1 (rnad_observe_all) instead of cat / negate / swapaxes per slice (metric.py:66-81)."""
-        net.eval()
-        A = tree.max_actions
-        handle = tree.handle()
-        obs_row, obs_col = rnad_hip.observe_all(handle, self.joint_policy.device)
-        with torch.no_grad():
-            for lo in range(0, self.size, inference_batch_size):
-                hi = min(lo + inference_batch_size, self.size)
-                self.joint_policy[lo:hi, :A] = net.forward_policy(obs_row[lo:hi])  # row player
-                self.joint_policy[lo:hi, A:] = net.forward_policy(obs_col[lo:hi])  # column player
+        joint_policy_of(tree, net, out=self.joint_policy, inference_batch_size=inference_batch_size)
         self.get_nashconv(tree, self.joint_policy)
         net.train()
 
@@ -64,6 +59,71 @@ class NashConvData:
             idx = self.depth == depth
             means[depth] = torch.mean(nashconv[idx]).item()
         return means
+
+
+def joint_policy_of(tree, net, out: torch.Tensor = None, inference_batch_size: int = 10**5) -> torch.Tensor:
+    """The net's policy at every state for both players, [S, 2A]: row player's in [:A], column player's in [A:] (the inference half of
+    get_nashconv_from_net, metric.py:60-82).  out: an existing [S, 2A] fp32 table (or a view of one) on the tree's device to fill.
+    The net is evaluated in eval mode and left in the mode it came in."""
+    S, A = tree.value_tensor.shape[0], tree.max_actions
+    if out is None:
+        out = torch.zeros((S, 2 * A), device=tree.device, dtype=torch.float)
+    assert tuple(out.shape) == (S, 2 * A) and out.dtype == torch.float
+    obs_row, obs_col = rnad_hip.observe_all(tree.handle(), out.device)
+    was_training = net.training
+    net.eval()
+    with torch.no_grad():
+        for lo in range(0, S, inference_batch_size):
+            hi = min(lo + inference_batch_size, S)
+            out[lo:hi, :A] = net.forward_policy(obs_row[lo:hi])  # row player
+            out[lo:hi, A:] = net.forward_policy(obs_col[lo:hi])  # column player
+    net.train(was_training)
+    return out
+
+
+class CrossPlay(NamedTuple):
+    """cross_play's result, tensors on the tree's device.  payoff[i, j]: expected payoff of the row player at the root when player i
+    plays the rows and player j the columns (the column player's is its negative); values [S, n, n]: the same at every state;
+    nashconv [n]: row_best[1] + col_best[1] of get_nashconv per player; exploitability [n, 2]: what a best response gains over the
+    player's self-play value against its column side (row_best[1] - payoff[k, k]) and against its row side (col_best[1] + payoff[k, k]).
+    The two are >= 0 up to rounding and sum to nashconv[k]."""
+
+    payoff: torch.Tensor
+    values: torch.Tensor
+    nashconv: torch.Tensor
+    exploitability: torch.Tensor
+
+
+def cross_play(tree, players) -> CrossPlay:
+    """Exact cross-play of `players` on the enumerated tree: each is a net (forward_policy) or a ready [S, 2A] policy table in the
+    layout of NashConvData.joint_policy.  No games are sampled: rnad_cross_play sweeps the tree once for all pairs."""
+    players = list(players)
+    n = len(players)
+    if not 1 <= n <= rnad_hip.CROSS_PLAY_MAX:
+        raise ValueError(f"cross_play takes 1 to {rnad_hip.CROSS_PLAY_MAX} players, got {n}")
+    S, A = tree.value_tensor.shape[0], tree.max_actions
+    handle = tree.handle()
+    dev = tree.value_tensor.device
+    policies = torch.zeros((S, n, 2 * A), device=dev, dtype=torch.float)
+    for k, player in enumerate(players):
+        if torch.is_tensor(player):
+            if tuple(player.shape) != (S, 2 * A):
+                raise ValueError(f"player {k}: a policy table must be [{S}, {2 * A}], got {tuple(player.shape)}")
+            policies[:, k] = player.detach().to(device=dev, dtype=torch.float)
+        else:
+            joint_policy_of(tree, player, out=policies[:, k])
+    values = rnad_hip.cross_play(handle, policies)
+    payoff = values[1].clone()
+    data = NashConvData(tree)
+    best = []
+    for k in range(n):
+        data.joint_policy.copy_(policies[:, k])
+        data.get_nashconv(tree, data.joint_policy)
+        best.append(torch.stack([data.row_best[1], data.col_best[1]]))
+    best = torch.stack(best)  # [n, 2]
+    diag = torch.diagonal(payoff)
+    exploitability = torch.stack([best[:, 0] - diag, best[:, 1] + diag], dim=1)
+    return CrossPlay(payoff=payoff, values=values, nashconv=best[:, 0] + best[:, 1], exploitability=exploitability)
 
 
 def kld(p: torch.Tensor, q: torch.Tensor, valid: torch.Tensor, legal_actions: torch.Tensor, valid_count: int = None):
