@@ -24,6 +24,7 @@ done
 [ -f $O/parity_errors.json ] && cp $O/parity_errors.json $P/${tag}_parity_errors.json
 [ -f $O/mlp_bwd_errors_fp32_torch.json ] && python tools/mlp_bwd_errors.py $O $P/mlp_bwd_errors.json  # (pytest run with RNAD_ERRORS_DIR=$O)
 [ -f $O/mlp_fwd_errors_fp32_torch.json ] && python tools/mlp_fwd_errors.py $O $P/mlp_fwd_errors.json  # (likewise)
+[ -f $O/learn_errors_cpu.json ] && python tools/learn_errors.py $O $P/learn_errors.json  # (likewise)
 [ -f $O/e2e_stats.jsonl ] && cp $O/e2e_stats.jsonl $P/${tag}_e2e_stats.jsonl
 [ -f $O/${tag}_pytest_gpu.log ] && tail -400 $O/${tag}_pytest_gpu.log > $P/${tag}_pytest_gpu.log
 ls $P | grep "^${tag}" | wc -l
