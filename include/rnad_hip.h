@@ -808,6 +808,36 @@ int64_t rnad_cross_play_size(int64_t S, int n);
 int rnad_cross_play(const rnad_tree_t *tree, int n, const float *policies, float *values, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact tabular R-NaD  --  no counterpart in the reference, which only samples: the fixed point of
+ * ONE regularisation update (learn/rnad.py:530-531 swaps the regularisation net) on the enumerated
+ * tree, by backward induction.  For every state s reachable from the root, with
+ *   Q[s,r,c] = sum_t chance[s,t,r,c] * (next == 0 ? value[s,t,r,c] : V[next])   (chance <= 0 skipped)
+ * the call finds the unique pair
+ *   pi_row ~ mu_row * exp((Q pi_col) / eta)      pi_col ~ mu_col * exp(-(Q^T pi_row) / eta)
+ *   V[s] = pi_row^T Q pi_col - eta * KL(pi_row || mu_row) + eta * KL(pi_col || mu_col),   V[0] = 0
+ * V is the row player's regularised value, the sign of player_others in learn/vtrace.py:234-239.
+ * log_reg f32 [S][2A] (device): log mu in the layout of NashConvData.joint_policy; -inf puts an
+ * action outside the support, entries of illegal actions are ignored.  mu enters the KL terms as it
+ * is given: a table that sums to k shifts a player's KL by -log k.  Outside the support pi = 0,
+ * log pi = -inf, and no 0 * inf arises.  Every entry of log_reg must be below +inf (a log of a
+ * probability is <= 0): the call cannot look at device data, and +inf or NaN there gives NaN outputs
+ * for that state.
+ * Each state iterates on log pi in registers (extragradient on the magnet mirror-descent step,
+ * tau = 1 / (2 max|Q|), csrc/reg_solve.hip) until its residual
+ *   max_a |pi(a) - softmax(log mu + q / eta)(a)|,  q = (Q pi_col, -Q^T pi_row),  both players
+ * is <= tol or max_iters steps are spent.
+ * Outputs (device): log_policy, policy f32 [S][2A]; values, residual f32 [S] (the last residual the
+ * state evaluated); iters int32 [S] (steps spent: == max_iters with residual > tol means not
+ * converged -- reported, not hidden).  State 0 and unreachable states: zeros, log_policy -inf.
+ * One launch that writes those rows, then one per level, bottom-up, on `stream`; nothing is
+ * allocated, no atomics, a fixed order of operations: the same inputs give the same bits and the
+ * call can be captured.  Refused on the host: eta <= 0, tol <= 0, max_iters < 1, a null pointer, an
+ * output that overlaps log_reg or another output.
+ * ---------------------------------------------------------------------------------------------- */
+int rnad_reg_solve(const rnad_tree_t *tree, float eta, float tol, int max_iters, const float *log_reg, float *log_policy, float *policy,
+                   float *values, float *residual, int32_t *iters, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Native tree generator (HOST code)  --  environment/tree.py:164-366 (generate, _transition_probs,
  * _solve) for trees too large for the Python recursion (66 431 states take > 100 s there).
  * Regular shape only: every state has A x A legal actions and depth_bound - 1 below it; chance

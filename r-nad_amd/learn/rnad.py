@@ -446,6 +446,15 @@ class RNaD:
             raise ValueError("cross_play: this trainer is not initialised")
         return metric.cross_play(self.tree, [self.net_target] + [other.net_target for other in others])
 
+    def tabular_baseline(self, updates: int):
+        """NashConv after each of `updates` exact regularisation updates at this trainer's eta, from the uniform magnet
+        (learn.tabular.TabularRNaD): the curve R-NaD itself would follow on this tree without sampling and without a net."""
+        from learn import tabular
+
+        if not self.eta > 0:
+            raise ValueError("tabular_baseline: eta = 0: the unregularised game has no unique fixed point to sweep to")
+        return list(tabular.TabularRNaD(self.tree, self.eta).run(updates))
+
     def _grad_bucket(self, weights):
         """One flat fp32 buffer holding the learner's gradients back to back (the RCCL bucket) and per-tensor views of it."""
         n = sum(w.numel() for w in weights)

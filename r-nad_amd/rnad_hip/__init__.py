@@ -1925,6 +1925,43 @@ def cross_play(tree, policies, values=None):
     return values
 
 
+def reg_solve(tree, eta, log_reg, tol=1e-5, max_iters=4096, log_policy=None, policy=None, values=None, residual=None, iters=None):
+    """rnad_reg_solve: the fixed point of one regularisation update at every state, by backward induction.  log_reg f32 [S, 2A]: log mu in
+    the layout of NashConvData.joint_policy (-inf: outside the support) -> (log_policy [S, 2A], policy [S, 2A], values [S], residual [S],
+    iters int32 [S]); iters == max_iters with residual > tol marks a state that did not converge.  The five outputs may be given as
+    existing buffers (every row is written).  With all five given nothing is allocated: capturable."""
+    if not torch.is_tensor(log_reg) or log_reg.dim() != 2:
+        raise RnadHipError("reg_solve: log_reg must be a tensor of shape [S, 2A]")
+    rp = _dp(log_reg, F32, "log_reg")
+    if not isinstance(tree, TreeHandle):
+        raise RnadHipError("reg_solve: tree must be a TreeHandle (Tree.handle())")
+    S, A = tree.S, tree.A
+    if tuple(log_reg.shape) != (S, 2 * A):
+        raise RnadHipError(f"reg_solve: log_reg of shape {tuple(log_reg.shape)} does not fit a tree of {S} states and {A} actions "
+                           f"(expected [{S}, {2 * A}])")
+    if log_reg.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
+        raise RnadHipError(f"reg_solve: log_reg lives on {log_reg.device}, the tree's tables on {tree.device}")
+    eta, tol, max_iters = float(eta), float(tol), int(max_iters)
+    if not eta > 0:
+        raise RnadHipError(f"reg_solve: eta = {eta} is not positive (the unregularised game has no unique fixed point)")
+    if not tol > 0 or max_iters < 1:
+        raise RnadHipError(f"reg_solve: tol = {tol} must be positive and max_iters = {max_iters} at least 1")
+    outs, ptrs = [], []
+    for name, given, shape, dtype in (("log_policy", log_policy, (S, 2 * A), F32), ("policy", policy, (S, 2 * A), F32),
+                                      ("values", values, (S,), F32), ("residual", residual, (S,), F32), ("iters", iters, (S,), I32)):
+        t = torch.empty(shape, dtype=dtype, device=log_reg.device) if given is None else given
+        ptrs.append(_dp(t, dtype, name))
+        if tuple(t.shape) != shape or t.device != log_reg.device:
+            raise RnadHipError(f"reg_solve: {name} must be {list(shape)} on {log_reg.device}, got {list(t.shape)} on {t.device}")
+        for other_name, other in [("log_reg", log_reg)] + list(zip(("log_policy", "policy", "values", "residual", "iters"), outs)):
+            lo, hi = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
+            if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+                raise RnadHipError(f"reg_solve: {name} aliases {other_name} (the buffers overlap)")
+        outs.append(t)
+    _check(lib().rnad_reg_solve(tree.ptr, eta, tol, max_iters, rp, *ptrs, _stream()))
+    return tuple(outs)
+
+
 # --------------------------------------------------------------------------------------- host-side: generator / solver
 def solve_matrix(M, max_actions):
     """tree.py:199-234 for one fp32 matrix (CPU tensor [ra, ca]) -> (solution [2*max_actions], value)."""
