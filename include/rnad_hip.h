@@ -808,6 +808,34 @@ int64_t rnad_cross_play_size(int64_t S, int n);
 int rnad_cross_play(const rnad_tree_t *tree, int n, const float *policies, float *values, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixtures of whole policies  --  no counterpart in the reference.  "Draw member k with probability
+ * w[k], then play J_k to the end" is, by Kuhn's theorem, the behaviour policy that weights member k
+ * at a state with the probability that k's OWN actions lead there -- not the state-wise average of
+ * the tables.  A link (s, r, c, t) -> u is live when chance > 0 and next != 0.
+ *   reach[1, side, k] = 1
+ *   reach[u, 0, k]    = reach[s, 0, k] * J_k[s, r]            reach[u, 1, k] = reach[s, 1, k] * J_k[s, A + c]
+ *   D[s, side]        = sum_k w[side, k] * reach[s, side, k]
+ *   mix[s, side*A+a]  = sum_k w[side, k] * reach[s, side, k] * J_k[s, side*A + a] / D[s, side]   where D > 0
+ *                     = sum_k w[side, k] * J_k[s, side*A + a]                                     where D == 0
+ * (D == 0: the mixture's own player never comes to s and nothing at the root depends on the row.)
+ * The orientation is that of rnad_cross_play; it is not the joint reach of rnad_nashconv
+ * (pi[A + r] * pi[c] * chance, one table).  The index tensor must be a tree: with two live links to
+ * one state the own-action reach is undefined, and which of them is kept is not specified
+ * (util.metric.mixture refuses such a tree; this call cannot look at device data).
+ * policies f32 [S][n][2A] (device) as for rnad_cross_play; weights f32 [2][n] (device): the row
+ * side's, then the column side's, nonnegative, each side summing to 1.  Outputs (device), both the
+ * caller's: mix f32 [S][2A], reach f32 [S][2][n].  Every row is written -- state 0 and states no
+ * live path reaches with zeros -- and nothing is allocated or cleared otherwise, so the call can be
+ * captured in a hipGraph.  One launch that writes those rows and the root's reach, then one per
+ * level, top-down, on `stream`; no atomics and a fixed summation order: the same inputs give the
+ * same bits.  Neither output may overlap policies or weights.
+ * rnad_mixture_size (host only): floats of `reach` = 2 * S * n; -1 unless S >= 2 and
+ * 1 <= n <= RNAD_CROSS_PLAY_MAX.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t rnad_mixture_size(int64_t S, int n);
+int rnad_mixture(const rnad_tree_t *tree, int n, const float *policies, const float *weights, float *mix, float *reach, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact tabular R-NaD  --  no counterpart in the reference, which only samples: the fixed point of
  * ONE regularisation update (learn/rnad.py:530-531 swaps the regularisation net) on the enumerated
  * tree, by backward induction.  For every state s reachable from the root, with

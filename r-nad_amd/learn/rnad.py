@@ -435,16 +435,24 @@ class RNaD:
     def cross_play(self, *others) -> "metric.CrossPlay":
         """Exact payoff matrix of this trainer's target net (player 0) against the target nets of `others`, trainers over the same tree
         (the `for eta in ...` runs of main.py:55-81): util.metric.cross_play, no sampled games.  Another tree is refused, by its hash."""
+        return metric.cross_play(self.tree, self._target_nets("cross_play", others))
+
+    def population(self, *others) -> "metric.Population":
+        """cross_play's twin for mixtures: the meta-Nash and the uniform mixture of this trainer's target net and those of `others`, as
+        policy tables with their NashConv (util.metric.population).  The same refusals."""
+        return metric.population(self.tree, self._target_nets("population", others))
+
+    def _target_nets(self, what, others):
         for k, other in enumerate(others):
             if other.tree is not self.tree and (other.tree.hash != self.tree.hash
                                                 or other.tree.value_tensor.shape != self.tree.value_tensor.shape):
-                raise ValueError(f"cross_play: trainer {k + 1} ('{other.directory_name}') plays another tree "
+                raise ValueError(f"{what}: trainer {k + 1} ('{other.directory_name}') plays another tree "
                                  f"(hash {other.tree.hash} != {self.tree.hash})")
             if other.net_target is None:
-                raise ValueError(f"cross_play: trainer {k + 1} ('{other.directory_name}') is not initialised")
+                raise ValueError(f"{what}: trainer {k + 1} ('{other.directory_name}') is not initialised")
         if self.net_target is None:
-            raise ValueError("cross_play: this trainer is not initialised")
-        return metric.cross_play(self.tree, [self.net_target] + [other.net_target for other in others])
+            raise ValueError(f"{what}: this trainer is not initialised")
+        return [self.net_target] + [other.net_target for other in others]
 
     def tabular_baseline(self, updates: int):
         """NashConv after each of `updates` exact regularisation updates at this trainer's eta, from the uniform magnet

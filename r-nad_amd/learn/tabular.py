@@ -78,9 +78,11 @@ def solve_regularized(tree, eta, reg=None, tol=1e-5, max_iters=4096) -> RegSolut
 class TabularRNaD:
     """R-NaD's outer loop with every inner loop replaced by its exact fixed point.  update(): solve for the current magnet, then mu <- pi
     (the log table is handed on, so a magnet far below e^-500 survives).  nashconv_history[m]: NashConv of the policy after update m + 1
-    (NashConvData.get_nashconv); unconverged_history[m]: the states of that solve that did not reach tol."""
+    (NashConvData.get_nashconv); unconverged_history[m]: the states of that solve that did not reach tol.  average=True also keeps
+    average_policy, the exact uniform mixture of the policies of all updates so far (util.metric.mixture: update m + 1 folds in as the
+    mixture of the average and the new policy with weights m and 1), and its NashConv in average_nashconv_history."""
 
-    def __init__(self, tree, eta, tol=1e-5, max_iters=4096, reg=None):
+    def __init__(self, tree, eta, tol=1e-5, max_iters=4096, reg=None, average=False):
         if not float(eta) > 0:
             raise ValueError(f"TabularRNaD: eta = {eta}: the unregularised game has no unique fixed point to sweep to")
         self.tree, self.eta, self.tol, self.max_iters = tree, float(eta), float(tol), int(max_iters)
@@ -89,6 +91,9 @@ class TabularRNaD:
         self.nashconv_history: List[float] = []
         self.unconverged_history: List[int] = []
         self._data = metric.NashConvData(tree)
+        self.average = bool(average)
+        self.average_policy = None
+        self.average_nashconv_history: List[float] = []
 
     @property
     def policy(self) -> torch.Tensor:
@@ -108,6 +113,13 @@ class TabularRNaD:
         self._data.get_nashconv(self.tree, self._data.joint_policy)
         self.nashconv_history.append((self._data.row_best[1] + self._data.col_best[1]).item())
         self.unconverged_history.append(self.solution.unconverged)
+        if self.average:
+            m = len(self.average_nashconv_history)
+            self.average_policy = (self.solution.policy.clone() if m == 0 else
+                                   metric.mixture(self.tree, [self.average_policy, self.solution.policy], [m, 1]).policy)
+            self._data.joint_policy.copy_(self.average_policy)
+            self._data.get_nashconv(self.tree, self._data.joint_policy)
+            self.average_nashconv_history.append((self._data.row_best[1] + self._data.col_best[1]).item())
         return self.nashconv_history[-1]
 
     def run(self, updates: int) -> List[float]:

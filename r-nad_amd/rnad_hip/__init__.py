@@ -1925,6 +1925,42 @@ def cross_play(tree, policies, values=None):
     return values
 
 
+def mixture(tree, policies, weights, mix=None, reach=None):
+    """rnad_mixture: policies f32 [S, n, 2A] as for cross_play, weights f32 [2, n] on the device (row side, column side; nonnegative, each
+    side summing to 1) -> (mix f32 [S, 2A], reach f32 [S, 2, n]): the behaviour policy that plays like the mixture of the n whole policies,
+    and every member's own-action reach.  mix, reach: existing buffers to fill (every row is written).  With both given nothing is
+    allocated: capturable."""
+    if not torch.is_tensor(policies) or policies.dim() != 3:
+        raise RnadHipError("mixture: policies must be a tensor of shape [S, n, 2A]")
+    pp = _dp(policies, F32, "policies")
+    if not isinstance(tree, TreeHandle):
+        raise RnadHipError("mixture: tree must be a TreeHandle (Tree.handle())")
+    S, n, A2 = policies.shape
+    if S != tree.S or A2 != 2 * tree.A:
+        raise RnadHipError(f"mixture: policies of shape {tuple(policies.shape)} do not fit a tree of {tree.S} states and {tree.A} actions "
+                           f"(expected [{tree.S}, n, {2 * tree.A}])")
+    if lib().rnad_mixture_size(S, n) < 0:
+        raise RnadHipError(f"mixture: {n} policies outside [1, {CROSS_PLAY_MAX}]")
+    if policies.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
+        raise RnadHipError(f"mixture: policies live on {policies.device}, the tree's tables on {tree.device}")
+    if mix is None:
+        mix = torch.empty((S, A2), dtype=F32, device=policies.device)
+    if reach is None:
+        reach = torch.empty((S, 2, n), dtype=F32, device=policies.device)
+    ptrs = []
+    lo, hi = policies.data_ptr(), policies.data_ptr() + policies.numel() * policies.element_size()
+    for name, t, shape in (("weights", weights, (2, n)), ("mix", mix, (S, A2)), ("reach", reach, (S, 2, n))):
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"mixture: {name} must be a tensor of shape {list(shape)}")
+        ptrs.append(_dp(t, F32, name))
+        if tuple(t.shape) != shape or t.device != policies.device:
+            raise RnadHipError(f"mixture: {name} must be {list(shape)} on {policies.device}, got {list(t.shape)} on {t.device}")
+        if name != "weights" and t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+            raise RnadHipError(f"mixture: {name} aliases policies (the buffers overlap)")
+    _check(lib().rnad_mixture(tree.ptr, n, pp, *ptrs, _stream()))
+    return mix, reach
+
+
 def reg_solve(tree, eta, log_reg, tol=1e-5, max_iters=4096, log_policy=None, policy=None, values=None, residual=None, iters=None):
     """rnad_reg_solve: the fixed point of one regularisation update at every state, by backward induction.  log_reg f32 [S, 2A]: log mu in
     the layout of NashConvData.joint_policy (-inf: outside the support) -> (log_policy [S, 2A], policy [S, 2A], values [S], residual [S],
