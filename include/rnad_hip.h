@@ -836,6 +836,43 @@ int64_t rnad_mixture_size(int64_t S, int n);
 int rnad_mixture(const rnad_tree_t *tree, int n, const float *policies, const float *weights, float *mix, float *reach, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Best responses as policies  --  no counterpart in the reference, whose get_nashconv
+ * (util/metric.py:134-175) keeps the best-response VALUES of one table and drops the action that
+ * attains them.  For each of n tables, side 0 is the row player responding to table k's column side,
+ * side 1 the column player responding to its row side:
+ *   m[s, r, c]          = sum_t chance[s,t,r,c] * (next == 0 ? +-value : values[next, side, k])
+ *                         (chance <= 0 skipped; side 1 counts a terminal payoff as -value)
+ *   q[s, 0, k, r]       = sum_c m[s, r, c] * J_k[s, A + c]       q[s, 1, k, c] = sum_r J_k[s, r] * m[s, r, c]
+ *   values[s, side, k]  = max over the side's legal actions a of q[s, side, k, a]
+ *   best[s, k, side*A + a] = 1 at the maximising legal action, 0 elsewhere; ties go to the lowest index
+ *   gain[s, side, k]    = values[s, side, k] - sum over legal a of J_k[s, side*A + a] * q[s, side, k, a]
+ *   reach[1, k] = 1,  reach[u, k] = reach[s, k] * (J_k[s, r] * J_k[s, A + c]) * chance
+ *                         for every live link (s, r, c, t) -> u  (chance > 0, next != 0)
+ * reach is table k's own JOINT reach, chance included, in the orientation of rnad_cross_play; it is
+ * not the pi[A + r] * pi[c] product rnad_nashconv keeps from the reference's reach sweep (:130-132).
+ * With it the performance-difference identity holds per side and per table,
+ *   values[1, side, k] -+ U[k, k]  =  sum_s reach[s, k] * gain[s, side, k]
+ * so reach * gain attributes a table's exploitability to states.  The sums keep the operation order
+ * of rnad_nashconv's bottom-up sweep: values[:, 0, k] and values[:, 1, k] carry the bits of its
+ * row_best and col_best for table k started at the root.  A reached state whose side has no legal
+ * action gets -inf there and a zero row of best.  The index tensor must be a tree: two live links to
+ * one state would race for its reach (util.metric.best_response refuses such a tree; this call
+ * cannot look at device data).
+ * policies f32 [S][n][2A] (device) as for rnad_cross_play.  Outputs (device), all four required and
+ * the caller's: best f32 [S][n][2A] -- best[:, k] is an ordinary policy table --, values and gain
+ * f32 [S][2][n], reach f32 [S][n].  Every row is written -- state 0 and states no live path reaches
+ * with zeros -- and nothing is allocated or cleared otherwise, so the call can be captured in a
+ * hipGraph.  One launch that writes those rows and the root's reach, one per level bottom-up, then
+ * one per level top-down, on `stream`; no atomics and a fixed summation order: the same inputs give
+ * the same bits.  The transition table is read once per 32 tables.  No output may overlap policies.
+ * rnad_best_response_size (host only): floats of `values` (and of `gain`) = 2 * S * n; -1 unless
+ * S >= 2 and 1 <= n <= RNAD_CROSS_PLAY_MAX.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t rnad_best_response_size(int64_t S, int n);
+int rnad_best_response(const rnad_tree_t *tree, int n, const float *policies, float *best, float *values, float *gain, float *reach,
+                       void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact tabular R-NaD  --  no counterpart in the reference, which only samples: the fixed point of
  * ONE regularisation update (learn/rnad.py:530-531 swaps the regularisation net) on the enumerated
  * tree, by backward induction.  For every state s reachable from the root, with

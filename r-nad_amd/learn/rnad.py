@@ -442,6 +442,11 @@ class RNaD:
         policy tables with their NashConv (util.metric.population).  The same refusals."""
         return metric.population(self.tree, self._target_nets("population", others))
 
+    def best_response(self, *others) -> "metric.BestResponse":
+        """cross_play's twin for exploiters: the exact best response to this trainer's target net (player 0) and to those of `others`
+        as policy tables, with the states each net is exploited at (util.metric.best_response).  The same refusals."""
+        return metric.best_response(self.tree, self._target_nets("best_response", others))
+
     def _target_nets(self, what, others):
         for k, other in enumerate(others):
             if other.tree is not self.tree and (other.tree.hash != self.tree.hash

@@ -1961,6 +1961,41 @@ def mixture(tree, policies, weights, mix=None, reach=None):
     return mix, reach
 
 
+def best_response(tree, policies, best=None, values=None, gain=None, reach=None):
+    """rnad_best_response: policies f32 [S, n, 2A] as for cross_play -> (best f32 [S, n, 2A], values f32 [S, 2, n], gain f32 [S, 2, n],
+    reach f32 [S, n]): per table k the best response of the row player to k's column side (side 0) and of the column player to its row
+    side (side 1) as a one-hot policy table best[:, k], its value at every state (the row_best / col_best of nashconv, bit for bit), what
+    it gains there over table k's own play, and table k's joint reach; sum_s reach * gain is k's exploitability per side.  best, values,
+    gain, reach: existing buffers to fill (every row is written).  With all four given nothing is allocated: capturable."""
+    if not torch.is_tensor(policies) or policies.dim() != 3:
+        raise RnadHipError("best_response: policies must be a tensor of shape [S, n, 2A]")
+    pp = _dp(policies, F32, "policies")
+    if not isinstance(tree, TreeHandle):
+        raise RnadHipError("best_response: tree must be a TreeHandle (Tree.handle())")
+    S, n, A2 = policies.shape
+    if S != tree.S or A2 != 2 * tree.A:
+        raise RnadHipError(f"best_response: policies of shape {tuple(policies.shape)} do not fit a tree of {tree.S} states and {tree.A} "
+                           f"actions (expected [{tree.S}, n, {2 * tree.A}])")
+    if lib().rnad_best_response_size(S, n) < 0:
+        raise RnadHipError(f"best_response: {n} policies outside [1, {CROSS_PLAY_MAX}]")
+    if policies.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
+        raise RnadHipError(f"best_response: policies live on {policies.device}, the tree's tables on {tree.device}")
+    outs, ptrs = [], []
+    lo, hi = policies.data_ptr(), policies.data_ptr() + policies.numel() * policies.element_size()
+    for name, given, shape in (("best", best, (S, n, A2)), ("values", values, (S, 2, n)), ("gain", gain, (S, 2, n)), ("reach", reach, (S, n))):
+        t = torch.empty(shape, dtype=F32, device=policies.device) if given is None else given
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"best_response: {name} must be a tensor of shape {list(shape)}")
+        ptrs.append(_dp(t, F32, name))
+        if tuple(t.shape) != shape or t.device != policies.device:
+            raise RnadHipError(f"best_response: {name} must be {list(shape)} on {policies.device}, got {list(t.shape)} on {t.device}")
+        if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+            raise RnadHipError(f"best_response: {name} aliases policies (the buffers overlap)")
+        outs.append(t)
+    _check(lib().rnad_best_response(tree.ptr, n, pp, *ptrs, _stream()))
+    return tuple(outs)
+
+
 def reg_solve(tree, eta, log_reg, tol=1e-5, max_iters=4096, log_policy=None, policy=None, values=None, residual=None, iters=None):
     """rnad_reg_solve: the fixed point of one regularisation update at every state, by backward induction.  log_reg f32 [S, 2A]: log mu in
     the layout of NashConvData.joint_policy (-inf: outside the support) -> (log_policy [S, 2A], policy [S, 2A], values [S], residual [S],

@@ -11,6 +11,9 @@ tables against each other (rnad_cross_play, one bottom-up sweep for all n * n pa
 `mixture(tree, players, weights)`, `meta_nash(payoff)` and `population(tree, players)` judge mixtures of whole policies, again
 without a counterpart: the behaviour policy that plays like the mixture (rnad_mixture, one top-down sweep of every member's
 own-action reach), the equilibrium weights of a payoff matrix, and the two together for a population.
+
+`best_response(tree, players)` gives what get_nashconv drops: the best response to each player as a policy table of its own, and the
+states at which the player loses its exploitability (rnad_best_response, one bottom-up and one top-down sweep for all players).
 """
 from typing import Dict, NamedTuple
 
@@ -224,6 +227,37 @@ def mixture(tree, players, weights=None, col_weights=None) -> Mixture:
     w = torch.stack([row, col]).to(dtype=torch.float).to(policies.device)
     mix, reach = rnad_hip.mixture(tree.handle(), policies, w)
     return Mixture(policy=mix, reach=reach, weights=w)
+
+
+class BestResponse(NamedTuple):
+    """best_response's result.  policy [S, n, 2A]: policy[:, k] is the exploiter of player k, an ordinary one-hot joint_policy table --
+    its row half the row player's best response to k's column side, its column half the column player's to k's row side; values
+    [S, 2, n]: the best-response values (row_best / col_best of get_nashconv for player k); gain [S, 2, n]: what the best action gains at
+    the state over k's own play of that side, with the best response below; reach [S, n]: player k's joint reach of the state, chance
+    included; attribution [S, 2, n] = reach[:, None] * gain: the share of k's exploitability the state accounts for.  These live on the
+    tree's device.  exploitability [n, 2]: the fp64 sum of attribution over the states, on the host -- by the performance-difference
+    identity what cross_play reports as exploitability, now as a sum over states."""
+
+    policy: torch.Tensor
+    values: torch.Tensor
+    gain: torch.Tensor
+    reach: torch.Tensor
+    attribution: torch.Tensor
+    exploitability: torch.Tensor
+
+
+def best_response(tree, players) -> BestResponse:
+    """The exact best response to each of `players` (nets or tables, as in cross_play) as a policy table, and where on the tree each
+    player is exploited: one bottom-up and one top-down sweep for all of them (rnad_best_response).  policy[:, k] plays like any other
+    table: cross_play, mixture, population and solve_regularized(reg=...) take it as a player."""
+    policies = _policy_tables(tree, players, "best_response")
+    if not index_is_tree(tree):
+        raise ValueError("best_response: the index tensor is not a tree: joint reach is undefined (a state with two parents has no "
+                         "perfect recall, and its two reach values would race)")
+    best, values, gain, reach = rnad_hip.best_response(tree.handle(), policies)
+    attribution = reach[:, None, :] * gain
+    exploitability = attribution.to(torch.float64).sum(dim=0).t().contiguous().cpu()
+    return BestResponse(policy=best, values=values, gain=gain, reach=reach, attribution=attribution, exploitability=exploitability)
 
 
 def _simplex_max(T, basis, max_pivots):
