@@ -903,6 +903,41 @@ int rnad_reg_solve(const rnad_tree_t *tree, float eta, float tol, int max_iters,
                    float *values, float *residual, int32_t *iters, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact policy evaluation in the regularised game  --  no counterpart in the reference, whose
+ * learner estimates these quantities from sampled games (V-trace on transformed rewards,
+ * learn/vtrace.py:234-239).  For each of n (policy, magnet, eta) triples, bottom-up with V[0] = 0:
+ *   Q[s,r,c]      = sum_t chance[s,t,r,c] * (next == 0 ? value[s,t,r,c] : values[next, k])   (chance <= 0 skipped)
+ *   q[s,k,r]      = sum_c Q[s,r,c] * pi_k[s, A + c]        the row player's action values against k's column side
+ *   q[s,k,A + c]  = - sum_r pi_k[s, r] * Q[s,r,c]          the column player's, in its OWN payoff
+ *   KL_side       = sum over a with pi > 0 of pi[a] * (log pi[a] - log_reg[a])
+ *   values[s,k]   = sum_r pi_k[s,r] * q[s,k,r] - eta_k * KL_row + eta_k * KL_col     (rnad_reg_solve's V)
+ *   residual[s,k] = max over both sides and the side's support (legal and log_reg > -inf) of
+ *                   |pi(a) - softmax(log_reg + q / eta_k)(a)|             (rnad_reg_solve's residual)
+ * and top-down reach[1,k] = 1, reach[u,k] = reach[s,k] * (pi_k[s,r] * pi_k[s,A+c]) * chance for every
+ * live link: rnad_best_response's joint reach, by the same kernel, bit for bit.  q is the
+ * unregularised response: the logs enter values and residual only, so pi = 0 inside the magnet's
+ * support produces no infinity.  log_reg need not be normalised (a table that sums to c shifts a
+ * side's KL by -log c; the softmax and the fixed point do not change).  Absolute continuity is NOT
+ * checked: pi > 0 where log_reg = -inf gives an infinite KL by plain arithmetic
+ * (learn.tabular.evaluate_regularized refuses such input).  The index tensor must be a tree, as for
+ * rnad_best_response.
+ * eta: HOST array of n values, each > 0; they travel as kernel arguments, so a captured call keeps
+ * the values it was captured with.  policies, log_reg f32 [S][n][2A] (device).  Outputs (device),
+ * all four required and the caller's: values, residual, reach f32 [S][n], q f32 [S][n][2A].  Every
+ * row is written -- state 0 and states no live path reaches with zeros -- and nothing is allocated
+ * or cleared otherwise.  One launch that writes those rows and the root's reach, one per level
+ * bottom-up, one per level top-down, on `stream`; no atomics and a fixed order of operations: the
+ * same inputs give the same bits and the call can be captured in a hipGraph.  Refused on the host:
+ * a null pointer, n outside [1, RNAD_CROSS_PLAY_MAX], an eta that is not positive and finite, an
+ * output that overlaps an input or another output.
+ * rnad_reg_evaluate_size (host only): floats of `values` (and of residual, reach) = S * n; -1
+ * unless S >= 2 and 1 <= n <= RNAD_CROSS_PLAY_MAX.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t rnad_reg_evaluate_size(int64_t S, int n);
+int rnad_reg_evaluate(const rnad_tree_t *tree, int n, const float *eta, const float *policies, const float *log_reg, float *values,
+                      float *q, float *residual, float *reach, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Native tree generator (HOST code)  --  environment/tree.py:164-366 (generate, _transition_probs,
  * _solve) for trees too large for the Python recursion (66 431 states take > 100 s there).
  * Regular shape only: every state has A x A legal actions and depth_bound - 1 below it; chance

@@ -21,14 +21,13 @@
 // as in k_cross_play: the transition table is read once per 32 opponents, not once per opponent.  A child's values are two runs of n
 // consecutive floats.  The two sides differ only in which policy half they read, in the sign of a terminal payoff and in whether the
 // lane's own action is the row or the column of m: selects, no divergent branch.  Top-down: a wave per state, a lane per member.
-#include "common.hpp"
+// response_matrix and the top-down kernel (k_joint_reach) live in tree_sweep.hpp, which reg_evaluate.hip shares.
+#include "tree_sweep.hpp"
 
 using namespace rnad;
+using namespace rnad::sweep;
 
 namespace {
-
-constexpr int kWaves = 4, kThreads = 64 * kWaves, kHalf = 32;
-static_assert(RNAD_CROSS_PLAY_MAX == kHalf, "a half-wave holds one side's members");
 
 // Rows the sweeps never write -- the absorbing state 0 and states no chance > 0 path reaches -- are zero in all four outputs, and the
 // root's reach is 1.  A kernel, not a memset node: see zero_async in common.hpp.
@@ -45,32 +44,6 @@ __global__ __launch_bounds__(kThreads) void k_best_response_init(const int32_t *
     for (int d = 0; d < n * A2; ++d) best[s * n * A2 + d] = 0.0f;
     for (int d = 0; d < 2 * n; ++d) values[s * 2 * n + d] = gain[s * 2 * n + d] = 0.0f;
     for (int k = 0; k < n; ++k) reach[s * n + k] = 0.0f;
-}
-
-// Per joint action the chance outcomes in order, as k_best_response sums them: m += (payoff or the child's value) * chance.  No branch: a
-// record without chance adds nothing through a select, and with CHILD a record that leaves the tree (or has no chance) reads row 0 of
-// `values` -- zeros, written by k_best_response_init earlier on the stream -- and discards it (k_cross_play's scheme).
-template <int A, bool CHILD>
-__device__ __forceinline__ void response_matrix(const uint32_t *rec, int C, bool col_side, const float *below, int stride,
-                                                float (&m)[A * A]) {
-    constexpr int AA = A * A;
-#pragma unroll
-    for (int rc = 0; rc < AA; ++rc) m[rc] = 0.0f;
-    for (int t = 0; t < C; ++t) {
-#pragma unroll
-        for (int rc = 0; rc < AA; ++rc) {
-            const uint32_t *x = rec + (rc * C + t) * 3;  // {next, chance, value}: the same address in every lane
-            const float chance = __uint_as_float(x[1]), value = __uint_as_float(x[2]);
-            const bool live = chance > 0.0f;
-            float v = col_side ? -value : value;  // terminal: row_b, col_b = v, -v (metric.py:141-144)
-            if (CHILD) {
-                const int next = live ? (int)x[0] : 0;
-                const float child = below[(int64_t)next * stride];
-                v = next == 0 ? v : child;
-            }
-            m[rc] = live ? m[rc] + v * chance : m[rc];
-        }
-    }
 }
 
 // One level, bottom-up: the four outputs' rows of its states from the finished levels below.  grid = ceil(n_states / kWaves).
@@ -137,40 +110,6 @@ __global__ __launch_bounds__(kThreads) void k_best_response_sweep(const Trans *_
     for (int a = 0; a < A; ++a) row[a] = a == arg ? 1.0f : 0.0f;
 }
 
-// One level, top-down: a wave per state hands the reach of its n tables on to every live child, n consecutive floats per child.  A tree
-// has one live link per state on average among its A * A * C records: the lanes look at 64 records at a time, read straight from the
-// table (coalesced; nothing is read twice, so nothing is staged), and the wave walks the set bits of the ballot, as k_mixture does.  Lane
-// k < n carries table k.  A thread per (state, table) that walks all records itself was measured at 5.50 ms against 3.00 ms on the
-// configs[3]-shaped tree at n = 32 (profiles/best_response_variants.md).
-template <int A>
-__global__ __launch_bounds__(kThreads) void k_best_response_reach(const Trans *__restrict__ trans, int C, const int32_t *__restrict__ order,
-                                                                  int64_t n_states, int n, const float *__restrict__ policies, float *reach) {
-    constexpr int AA = A * A;
-    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
-    const int64_t pos = (int64_t)blockIdx.x * kWaves + wave;
-    if (pos >= n_states) return;
-    const int s = order[pos];
-    const bool on = lane < n;
-    const int k = on ? lane : 0;
-    const float rs = reach[(int64_t)s * n + k];
-    const float *ps = policies + ((int64_t)s * n + k) * (2 * A);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(trans + (int64_t)s * AA * C);
-    for (int base = 0; base < AA * C; base += 64) {
-        const int d = base + lane;
-        const bool in = d < AA * C;
-        const int next_l = in ? (int)src[3 * d] : 0;
-        const float chance_l = in ? __uint_as_float(src[3 * d + 1]) : 0.0f;
-        const bool live = next_l != 0 && chance_l > 0.0f;
-        for (uint64_t todo = __ballot(live); todo != 0; todo &= todo - 1) {
-            const int bit = __ffsll((unsigned long long)todo) - 1, rc = (base + bit) / C;
-            const int64_t next = __shfl(next_l, bit);
-            const float chance = __shfl(chance_l, bit);
-            const float through = rs * (ps[rc / A] * ps[A + rc % A]);
-            if (on) reach[next * n + k] = through * chance;
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" int64_t rnad_best_response_size(int64_t S, int n) {
@@ -198,12 +137,7 @@ extern "C" int rnad_best_response(const rnad_tree_t *tree, int n, const float *p
                 hipLaunchKernelGGL((k_best_response_sweep<kA>), dim3((unsigned)((cnt + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream,
                                    tree->trans, tree->node, tree->C, tree->level_order + off, cnt, n, policies, best, values, gain);
         }
-        for (int l = 0; l < tree->n_levels; ++l) {
-            const int64_t off = tree->level_offsets[l], cnt = tree->level_offsets[l + 1] - off;
-            if (cnt > 0)
-                hipLaunchKernelGGL((k_best_response_reach<kA>), dim3((unsigned)((cnt + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream,
-                                   tree->trans, tree->C, tree->level_order + off, cnt, n, policies, reach);
-        }
+        launch_joint_reach<kA>(tree, n, policies, reach, stream);
     });
     RNAD_HIP_OK(hipGetLastError());
     return 0;

@@ -468,6 +468,33 @@ class RNaD:
             raise ValueError("tabular_baseline: eta = 0: the unregularised game has no unique fixed point to sweep to")
         return list(tabular.TabularRNaD(self.tree, self.eta).run(updates))
 
+    def inner_progress(self, alpha=None):
+        """How far the inner loop is from the fixed point its current magnet defines: learn.tabular.evaluate_regularized of
+        [net, net_target] at this trainer's eta against alpha * log pi_reg + (1 - alpha) * log pi_reg_ (:382), exactly, on the whole tree.
+        alpha=None: the schedule's alpha for the current n.  A term whose weight is exactly zero is skipped, as train_step skips it:
+        0 * -inf would poison the illegal entries.  Returns the RegEvaluation (member 0: net, member 1: net_target)."""
+        from learn import tabular
+
+        if not self.eta > 0:
+            raise ValueError("inner_progress: eta = 0: the unregularised game has no unique fixed point to measure against")
+        if self.net is None or self.net_target is None or self.net_reg is None or self.net_reg_ is None:
+            raise ValueError("inner_progress: this trainer is not initialised")
+        if alpha is None:
+            delta_m = self._steps_of_current_update()
+            if delta_m is None:
+                raise ValueError("inner_progress: training is over: the schedule has no alpha for this m; pass alpha")
+            alpha = self.alpha_of(self.n, delta_m)
+        alpha = float(alpha)
+        if not 0 <= alpha <= 1:
+            raise ValueError(f"inner_progress: alpha = {alpha} outside [0, 1]")
+        if alpha == 0:
+            magnet = tabular.log_reg_of(self.tree, self.net_reg_)
+        elif alpha == 1 or self._reg_nets_identical():
+            magnet = tabular.log_reg_of(self.tree, self.net_reg)
+        else:
+            magnet = alpha * tabular.log_reg_of(self.tree, self.net_reg) + (1 - alpha) * tabular.log_reg_of(self.tree, self.net_reg_)
+        return tabular.evaluate_regularized(self.tree, [self.net, self.net_target], self.eta, log_reg=magnet)
+
     def _grad_bucket(self, weights):
         """One flat fp32 buffer holding the learner's gradients back to back (the RCCL bucket) and per-tensor views of it."""
         n = sum(w.numel() for w in weights)

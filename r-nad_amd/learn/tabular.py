@@ -6,6 +6,10 @@ computes it for the whole tree in one bottom-up sweep (rnad_reg_solve, csrc/reg_
 regularisation policy (learn/rnad.py:530-531) and records NashConv after every update: the curve the algorithm itself would reach with
 sampling noise, off-policy correction and function approximation taken out.  The tables have the layout of NashConvData.joint_policy, so
 `util.metric.cross_play` plays them against trained nets as they are.
+
+`evaluate_regularized` answers the question in between: how far is an ARBITRARY policy from the fixed point its magnet defines, and what
+is it worth there (rnad_reg_evaluate, csrc/reg_evaluate.hip) -- the quantities the learner estimates by sampling.  `TabularNeuRD` is the
+exact inner loop built on it: NeuRD steps on a logit table, between `TabularRNaD` (no inner loop) and the sampled trainer.
 """
 from typing import List, NamedTuple
 
@@ -126,3 +130,182 @@ class TabularRNaD:
         for _ in range(int(updates)):
             self.update()
         return self.nashconv_history
+
+
+# ---------------------------------------------------------------------------------------------------- exact evaluation
+class RegEvaluation(NamedTuple):
+    """evaluate_regularized's result for n (policy, magnet, eta) triples; tensors on the tree's device unless said otherwise.
+    policy [S, n, 2A]: the tables as evaluated; values [S, n]: the row player's regularised value (solve_regularized's values for that
+    policy); q [S, n, 2A]: each side's unregularised action values against the other side, in its own payoff; residual [S, n]:
+    max_a |pi(a) - softmax(log mu + q / eta)(a)| over both sides, reg_solve's stopping quantity; reach [S, n]: the policy's joint reach,
+    chance included (best_response's); advantage [S, n, 2A] = q - eta * (log pi - log mu), centred by its pi-weighted mean per side, zero
+    outside the support and where pi = 0: the exact NeuRD direction, zero on the support at the fixed point; distance [n]: the fp64 sum
+    over the states of reach * residual, on the host; max_residual [n]: the largest residual over the states with reach > 0, on the host."""
+
+    policy: torch.Tensor
+    values: torch.Tensor
+    q: torch.Tensor
+    residual: torch.Tensor
+    reach: torch.Tensor
+    advantage: torch.Tensor
+    distance: torch.Tensor
+    max_residual: torch.Tensor
+
+
+def swept_states(tree) -> torch.Tensor:
+    """bool [S]: the states a sweep from the root visits (live links: chance > 0, index != 0).  Kept on the tree object for the tensors it
+    was computed from."""
+    index, chance = tree.index_tensor, tree.chance_tensor
+    key = (index.data_ptr(), chance.data_ptr(), index._version, chance._version)
+    cached = tree.__dict__.get("_swept_states")
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    live = (index != 0) & (chance > 0)
+    swept = torch.zeros((index.shape[0],), dtype=torch.bool, device=index.device)
+    frontier = torch.ones((1,), dtype=torch.long, device=index.device)
+    while frontier.numel() > 0:
+        swept[frontier] = True
+        frontier = index[frontier][live[frontier]].to(torch.long)
+    tree.__dict__["_swept_states"] = (key, swept)
+    return swept
+
+
+def _per_member(tree, tables, n, what) -> torch.Tensor:
+    """[S, n, 2A] fp32 on the tree's device from one [S, 2A] table for all members or a ready [S, n, 2A] one."""
+    S, A = tree.value_tensor.shape[0], tree.max_actions
+    t = tables.detach().to(device=tree.value_tensor.device, dtype=torch.float)
+    if tuple(t.shape) == (S, 2 * A):
+        t = t[:, None, :].expand(S, n, 2 * A)
+    if tuple(t.shape) != (S, n, 2 * A):
+        raise ValueError(f"{what}: a log table must be [{S}, {2 * A}] or [{S}, {n}, {2 * A}], got {tuple(tables.shape)}")
+    return t.contiguous()
+
+
+def neurd_advantage(tree, policies, log_policy, log_reg, q, eta, on) -> torch.Tensor:
+    """[S, n, 2A]: q - eta * (log pi - log mu), minus its pi-weighted mean per side, where `on`; zero elsewhere.  eta: [n] on the device.
+    log_policy: log pi as the caller holds it (finite where exp underflows)."""
+    A = tree.max_actions
+    zero = torch.zeros_like(q)
+    raw = torch.where(on, q - eta[None, :, None] * (torch.where(on, log_policy, zero) - torch.where(on, log_reg, zero)), zero)
+    mean = torch.cat([(policies[..., :A] * raw[..., :A]).sum(-1, keepdim=True).expand(-1, -1, A),
+                      (policies[..., A:] * raw[..., A:]).sum(-1, keepdim=True).expand(-1, -1, A)], dim=-1)
+    return torch.where(on, raw - mean, zero)
+
+
+def _evaluate(tree, policies, log_reg, etas, log_policy=None) -> RegEvaluation:
+    """policies, log_reg [S, n, 2A] on the device, etas: n positive floats.  Refuses mass outside the magnet's support at a swept state:
+    the KL there is infinite, and one such state poisons every value above it."""
+    if not metric.index_is_tree(tree):
+        raise ValueError("evaluate_regularized: the index tensor is not a tree: joint reach is undefined (a state with two parents has "
+                         "no perfect recall, and its two reach values would race)")
+    support = legal_mask(tree)[:, None, :] & (log_reg > float("-inf"))
+    outside = (policies > 0) & ~support & swept_states(tree)[:, None, None]
+    if bool(outside.any().item()):
+        s, k, a = (int(v) for v in outside.nonzero()[0])
+        raise ValueError(f"evaluate_regularized: player {k} puts probability {policies[s, k, a].item():.3g} on action {a} of state {s}, "
+                         "outside its magnet's support (illegal or mu = 0): the KL term is infinite")
+    values, q, residual, reach = rnad_hip.reg_evaluate(tree.handle(), etas, policies, log_reg)
+    eta_dev = torch.tensor(etas, dtype=torch.float, device=policies.device)
+    if log_policy is None:  # a table: where pi = 0 there is no log to take and no direction to report
+        advantage = neurd_advantage(tree, policies, torch.log(torch.where(policies > 0, policies, torch.ones_like(policies))), log_reg, q,
+                                    eta_dev, support & (policies > 0))
+    else:  # logits: an action whose probability underflowed still has its log and can come back
+        advantage = neurd_advantage(tree, policies, log_policy, log_reg, q, eta_dev, support)
+    distance = (reach.to(torch.float64) * residual.to(torch.float64)).sum(dim=0).cpu()
+    max_residual = torch.where(reach > 0, residual, torch.zeros_like(residual)).max(dim=0).values.to(torch.float64).cpu()
+    return RegEvaluation(policies, values, q, residual, reach, advantage, distance, max_residual)
+
+
+def evaluate_regularized(tree, players, eta, reg=None, log_reg=None) -> RegEvaluation:
+    """Exact evaluation of `players` (nets or [S, 2A] tables, as util.metric.cross_play takes them) in the game regularised towards a
+    magnet: their values, action values, distance to the magnet's fixed point and reach, in one sweep pair for up to 32 players.
+    eta: one positive number or one per player.  reg: None (the uniform magnet), one magnet for all players or a list of one per player,
+    each as log_reg_of takes it (a net or a probability table).  log_reg=: instead of reg, ready log tables [S, 2A] or [S, n, 2A] taken as
+    they are -- they need not be normalised (the trainer's alpha * log mu + (1 - alpha) * log mu_ is not)."""
+    policies = metric._policy_tables(tree, players, "evaluate_regularized")
+    n = policies.shape[1]
+    etas = [float(e) for e in eta] if hasattr(eta, "__len__") else [float(eta)] * n
+    if len(etas) != n:
+        raise ValueError(f"evaluate_regularized: {len(etas)} values of eta for {n} players")
+    if not all(e > 0 and e != float("inf") for e in etas):
+        raise ValueError(f"evaluate_regularized: eta = {etas}: the unregularised game has no unique fixed point to measure against")
+    if log_reg is not None:
+        if reg is not None:
+            raise ValueError("evaluate_regularized: give reg or log_reg, not both")
+        logs = _per_member(tree, log_reg, n, "log_reg")
+    elif isinstance(reg, (list, tuple)):
+        if len(reg) != n:
+            raise ValueError(f"evaluate_regularized: {len(reg)} magnets for {n} players")
+        logs = torch.stack([log_reg_of(tree, r) for r in reg], dim=1).contiguous()
+    else:
+        logs = _per_member(tree, log_reg_of(tree, reg), n, "reg")
+    return _evaluate(tree, policies, logs, etas)
+
+
+def softmax_support(logits) -> torch.Tensor:
+    """[S, 2A] policy of a logit table whose entries outside the support are -inf: a softmax per side, zero rows where a side has none."""
+    A = logits.shape[-1] // 2
+    halves = [torch.softmax(h, dim=-1) for h in (logits[..., :A], logits[..., A:])]
+    return torch.nan_to_num(torch.cat(halves, dim=-1), nan=0.0)
+
+
+def _log_softmax_support(logits) -> torch.Tensor:
+    A = logits.shape[-1] // 2
+    return torch.cat([torch.log_softmax(h, dim=-1) for h in (logits[..., :A], logits[..., A:])], dim=-1)
+
+
+class TabularNeuRD:
+    """R-NaD's inner loop made exact: NeuRD on a logit table l [S, 2A] with the advantage computed by a tree sweep instead of V-trace on
+    sampled games.  l starts at the magnet; entries outside the support (illegal, mu = 0) are -inf and never move.  step():
+    pi = softmax_support(l), evaluate pi (one rnad_reg_evaluate), l += lr * advantage with log pi taken as log_softmax(l) -- log(pi) of an
+    underflowed pi would be -inf.  At the fixed point of the magnet the advantage vanishes on the support.  run(steps) records distance and
+    max_residual (RegEvaluation) after every step in distance_history / residual_history (the evaluation of the new policy is kept and
+    serves the next step: one sweep pair per step); swap() makes the current policy the magnet, as
+    TabularRNaD.update does, so outer iterations compose.  lr * eta must stay below 1: the step multiplies log pi - log mu by 1 - lr * eta.
+    Not modelled: the logit-threshold gate and the gradient clip of get_loss_nerd (learn/vtrace.py), which act on a net's logits, and
+    everything sampling brings (importance weights, the thresholded acting policy)."""
+
+    def __init__(self, tree, eta, lr, reg=None):
+        if not float(eta) > 0:
+            raise ValueError(f"TabularNeuRD: eta = {eta}: the unregularised game has no unique fixed point to descend to")
+        if not float(lr) > 0 or float(lr) * float(eta) >= 1:
+            raise ValueError(f"TabularNeuRD: lr = {lr} with eta = {eta}: lr must be positive and lr * eta below 1")
+        self.tree, self.eta, self.lr = tree, float(eta), float(lr)
+        mask = legal_mask(tree)
+        log_reg = log_reg_of(tree, reg)
+        self.log_reg = torch.where(mask, log_reg, torch.full_like(log_reg, float("-inf"))).contiguous()
+        self.logits = self.log_reg.clone()
+        self.evaluation = None
+        self.distance_history: List[float] = []
+        self.residual_history: List[float] = []
+
+    @property
+    def policy(self) -> torch.Tensor:
+        """[S, 2A]: the policy of the current logits."""
+        return softmax_support(self.logits)
+
+    def evaluate(self) -> RegEvaluation:
+        """The current policy against the current magnet (no step)."""
+        return _evaluate(self.tree, self.policy[:, None, :].contiguous(), self.log_reg[:, None, :].contiguous(), [self.eta],
+                         log_policy=torch.nan_to_num(_log_softmax_support(self.logits), nan=0.0)[:, None, :])
+
+    def step(self) -> RegEvaluation:
+        """One NeuRD step; returns the evaluation of the policy the step started from."""
+        ev = self.evaluation if self.evaluation is not None else self.evaluate()
+        self.logits += self.lr * ev.advantage[:, 0]  # (-inf + 0 outside the support)
+        self.evaluation = None
+        return ev
+
+    def run(self, steps: int) -> List[float]:
+        for _ in range(int(steps)):
+            self.step()
+            self.evaluation = self.evaluate()
+            self.distance_history.append(float(self.evaluation.distance[0]))
+            self.residual_history.append(float(self.evaluation.max_residual[0]))
+        return self.residual_history
+
+    def swap(self) -> None:
+        """mu <- pi (learn/rnad.py:530-531): the log table is handed on, so a magnet far below e^-500 survives."""
+        self.log_reg = torch.where(self.logits > float("-inf"), _log_softmax_support(self.logits), self.logits).contiguous()
+        self.logits = self.log_reg.clone()
+        self.evaluation = None

@@ -2033,6 +2033,56 @@ def reg_solve(tree, eta, log_reg, tol=1e-5, max_iters=4096, log_policy=None, pol
     return tuple(outs)
 
 
+def reg_evaluate(tree, eta, policies, log_reg, values=None, q=None, residual=None, reach=None):
+    """rnad_reg_evaluate: exact evaluation of n (policy, magnet, eta) triples in the regularised game.  policies f32 [S, n, 2A] as for
+    cross_play, log_reg f32 [S, n, 2A] (log mu per member, -inf outside the support, not necessarily normalised), eta: n positive numbers
+    (or one for all) on the host -> (values [S, n]: the row player's regularised value, q [S, n, 2A]: each side's unregularised action
+    values in its own payoff, residual [S, n]: reg_solve's stopping quantity for the policy as given, reach [S, n]: best_response's joint
+    reach, bit for bit).  The four outputs may be given as existing buffers (every row is written).  With all four given nothing is
+    allocated on the device: capturable, and a captured call keeps the etas it was captured with."""
+    if not torch.is_tensor(policies) or policies.dim() != 3:
+        raise RnadHipError("reg_evaluate: policies must be a tensor of shape [S, n, 2A]")
+    pp = _dp(policies, F32, "policies")
+    if not isinstance(tree, TreeHandle):
+        raise RnadHipError("reg_evaluate: tree must be a TreeHandle (Tree.handle())")
+    S, n, A2 = policies.shape
+    if S != tree.S or A2 != 2 * tree.A:
+        raise RnadHipError(f"reg_evaluate: policies of shape {tuple(policies.shape)} do not fit a tree of {tree.S} states and {tree.A} "
+                           f"actions (expected [{tree.S}, n, {2 * tree.A}])")
+    if lib().rnad_reg_evaluate_size(S, n) < 0:
+        raise RnadHipError(f"reg_evaluate: {n} policies outside [1, {CROSS_PLAY_MAX}]")
+    if policies.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
+        raise RnadHipError(f"reg_evaluate: policies live on {policies.device}, the tree's tables on {tree.device}")
+    if not torch.is_tensor(log_reg):
+        raise RnadHipError(f"reg_evaluate: log_reg must be a tensor of shape [{S}, {n}, {A2}]")
+    rp = _dp(log_reg, F32, "log_reg")
+    if tuple(log_reg.shape) != (S, n, A2) or log_reg.device != policies.device:
+        raise RnadHipError(f"reg_evaluate: log_reg must be [{S}, {n}, {A2}] on {policies.device}, got {list(log_reg.shape)} on {log_reg.device}")
+    etas = [float(e) for e in (eta.tolist() if torch.is_tensor(eta) else eta)] if hasattr(eta, "__len__") else [float(eta)] * n
+    if len(etas) != n:
+        raise RnadHipError(f"reg_evaluate: {len(etas)} values of eta for {n} policies")
+    if not all(e > 0 and e != float("inf") for e in etas):
+        raise RnadHipError(f"reg_evaluate: eta = {etas} holds a value that is not positive and finite (the unregularised game has no "
+                           "fixed point to measure against)")
+    outs, ptrs = [], []
+    inputs = [("policies", policies), ("log_reg", log_reg)]
+    for name, given, shape in (("values", values, (S, n)), ("q", q, (S, n, A2)), ("residual", residual, (S, n)), ("reach", reach, (S, n))):
+        t = torch.empty(shape, dtype=F32, device=policies.device) if given is None else given
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"reg_evaluate: {name} must be a tensor of shape {list(shape)}")
+        ptrs.append(_dp(t, F32, name))
+        if tuple(t.shape) != shape or t.device != policies.device:
+            raise RnadHipError(f"reg_evaluate: {name} must be {list(shape)} on {policies.device}, got {list(t.shape)} on {t.device}")
+        for other_name, other in inputs + list(zip(("values", "q", "residual", "reach"), outs)):
+            lo, hi = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
+            if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+                raise RnadHipError(f"reg_evaluate: {name} aliases {other_name} (the buffers overlap)")
+        outs.append(t)
+    eta_c = (C.c_float * n)(*etas)
+    _check(lib().rnad_reg_evaluate(tree.ptr, n, C.cast(eta_c, C.c_void_p), pp, rp, *ptrs, _stream()))
+    return tuple(outs)
+
+
 # --------------------------------------------------------------------------------------- host-side: generator / solver
 def solve_matrix(M, max_actions):
     """tree.py:199-234 for one fp32 matrix (CPU tensor [ra, ca]) -> (solution [2*max_actions], value)."""
