@@ -938,6 +938,50 @@ int rnad_reg_evaluate(const rnad_tree_t *tree, int n, const float *eta, const fl
                       float *q, float *residual, float *reach, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact expected learner update  --  no counterpart in the reference, whose learner computes its
+ * value targets and action values from sampled games (two-player V-trace, learn/vtrace.py:206-322).
+ * For each of n members -- behaviour table mu, evaluated policy pip (pi_processed), lpol =
+ * log_pi - (alpha log_reg + (1 - alpha) log_reg_), the target net's value vv, and its own
+ * (eta, gamma, lambda, rho, c) -- the expectation, over complete episodes played by mu and the
+ * tree's chance, of what that program leaves at a (player, state) row given that the row is
+ * visited.  With cs = pip / mu (an action with mu = 0 is never drawn and is skipped),
+ * e[P] = sum_a pip lpol of side P, g = gamma, l = lambda, r the payoff of a record that leaves
+ * the tree, u its child otherwise, p its chance (p <= 0 skipped), bottom-up:
+ *   W0      = vv0 + sum_{a,b} mu0[a] mu1[b] (min(w, rho) (g eta e1 - eta e0 - vv0 + g sum_t p (u ? g vv0[u] : r))
+ *                                            + l g g min(w, c) sum_t p (u ? W0[u] - vv0[u] : 0)),   w = cs0[a] cs1[b]
+ *   q[0][a] = g eta e1 - eta lpol0[a] + g sum_b pip1[b] sum_t p (u ? g W0[u] : r)
+ *   W1[a]   = vv1 + sum_b mu1[b] sum_t p (u ? sum_a' mu0[u][a'] (min(w', rho) (g eta e0[u] - eta e1 + g g vv1[u] - vv1)
+ *                                                              + l g g min(w', c) (W1[u][a'] - vv1[u]))
+ *                                            : min(cs1[b], rho) (-r - eta e1 - vv1)),             w' = cs1[b] cs0[u][a']
+ *   q[1][b] = - eta lpol1[b] + sum_a mu0[a] sum_t p (u ? g eta e0[u] + g g sum_a' pip0[u][a'] W1[u][a'] : -r)
+ *   target[0] = W0,  target[1] = sum_a mu0[a] W1[a],  target_given_row = W1 (the column player's
+ *   target depends on the row action already taken at the state).  Where mu = 0 (never drawn, an
+ *   illegal action included) q keeps what the sampled program leaves there: vv - eta lpol.
+ * Top-down reach[1,k] = 1, reach[u,k] = reach[s,k] * (mu0[a] * mu1[b]) * chance: rnad_best_response's
+ * joint reach of the table mu, by the same kernel, bit for bit.
+ * hyper: HOST array [n][5] of (eta, gamma, lambda, rho, c); the values travel as kernel arguments,
+ * so a captured call keeps those it was captured with.  mu, pip, lpol f32 [S][n][2A], vv f32
+ * [S][n][2] (device).  Outputs (device), all required and the caller's: target f32 [S][n][2],
+ * target_given_row f32 [S][n][A], q f32 [S][n][2A], reach f32 [S][n]; workspace: f32,
+ * rnad_vtrace_expect_workspace(S, A, n) = S * n * (3A + 5) floats, in which every state leaves one
+ * record for its parent (its contents after the call are unspecified).  Every row is written --
+ * state 0 and states no live path reaches with zeros.  One launch that writes those rows and the
+ * root's reach, one per level bottom-up, one per level top-down, on `stream`; nothing is allocated,
+ * no atomics, a fixed order of operations: the same inputs give the same bits and the call can be
+ * captured in a hipGraph.  Refused on the host: a null pointer, n outside
+ * [1, RNAD_CROSS_PLAY_MAX], a tree of fewer than 2 states, a gamma that is not positive and finite,
+ * a negative clip, an eta or lambda that is not finite, an output that overlaps an input or
+ * another output.
+ * rnad_vtrace_expect_size (host only): floats of `reach` = S * n; -1 unless S >= 2 and
+ * 1 <= n <= RNAD_CROSS_PLAY_MAX.  rnad_vtrace_expect_workspace: -1 on the same conditions or an A
+ * outside [1, RNAD_MAX_ACTIONS].
+ * ---------------------------------------------------------------------------------------------- */
+int64_t rnad_vtrace_expect_size(int64_t S, int n);
+int64_t rnad_vtrace_expect_workspace(int64_t S, int A, int n);
+int rnad_vtrace_expect(const rnad_tree_t *tree, int n, const float *hyper, const float *mu, const float *pip, const float *lpol,
+                       const float *vv, float *target, float *target_given_row, float *q, float *reach, float *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Native tree generator (HOST code)  --  environment/tree.py:164-366 (generate, _transition_probs,
  * _solve) for trees too large for the Python recursion (66 431 states take > 100 s there).
  * Regular shape only: every state has A x A legal actions and depth_bound - 1 below it; chance

@@ -495,6 +495,26 @@ class RNaD:
             magnet = alpha * tabular.log_reg_of(self.tree, self.net_reg) + (1 - alpha) * tabular.log_reg_of(self.tree, self.net_reg_)
         return tabular.evaluate_regularized(self.tree, [self.net, self.net_target], self.eta, log_reg=magnet)
 
+    def expected_update(self, alpha=None):
+        """What the next learner step estimates, with the sampling taken out: learn.vtrace.expected_update of this trainer's four nets and
+        hyperparameters on the whole tree, the actor's policy -- the net's raw pi -- as the behaviour.  alpha=None: the schedule's alpha
+        for the current n.  Returns the ExpectedUpdate: the expected V-trace targets and action values per (player, state) row, the reach
+        under the actor, and the expected row gradients of the value and policy heads."""
+        from learn import vtrace
+
+        if self.net is None or self.net_target is None or self.net_reg is None or self.net_reg_ is None:
+            raise ValueError("expected_update: this trainer is not initialised")
+        if alpha is None:
+            delta_m = self._steps_of_current_update()
+            if delta_m is None:
+                raise ValueError("expected_update: training is over: the schedule has no alpha for this m; pass alpha")
+            alpha = self.alpha_of(self.n, delta_m)
+        alpha = float(alpha)
+        if not 0 <= alpha <= 1:
+            raise ValueError(f"expected_update: alpha = {alpha} outside [0, 1]")
+        return vtrace.expected_update(self.tree, self.net, self.net, None, self.net_target, self.net_reg, self.net_reg_,
+                                      self._learn_params(alpha))
+
     def _grad_bucket(self, weights):
         """One flat fp32 buffer holding the learner's gradients back to back (the RCCL bucket) and per-tensor views of it."""
         n = sum(w.numel() for w in weights)

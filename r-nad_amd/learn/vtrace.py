@@ -6,7 +6,7 @@ GPU tensors of the reference's shapes; they are made contiguous fp32/int32 for t
 go through these one by one -- it calls the fused kernel (rnad_hip.learn_fused) -- but they compute the same
 expressions in the same order and are what tests compare against the reference's fixtures.
 """
-from typing import Any, Sequence, Tuple
+from typing import Any, NamedTuple, Sequence, Tuple
 
 import torch
 
@@ -138,3 +138,148 @@ def get_loss_nerd(
         return _LossNerd.apply(logit_list[0], list(policy_list), qs, masks, legal_actions, float(clip), float(threshold))
     return sum(_LossNerd.apply(lg, [pi], [q], [m], legal_actions, float(clip), float(threshold))
                for lg, pi, q, m in zip(logit_list, policy_list, qs, masks))
+
+
+# ---------------------------------------------------------------------------------------------------- the exact expected update
+class ExpectedUpdate(NamedTuple):
+    """expected_update's result: what the learner's estimates are in expectation over complete episodes played by the behaviour; tensors
+    on the tree's device unless said otherwise, rows in the learner's layout (row = player * S + state).
+    pi_processed [2S, A]: the policy the targets evaluate; target [2S]: E[v_target at the slot | the row is visited]; target_given_row
+    [S, A]: the column player's target given the row action taken at the state; q [2S, A]: E[q at the slot | visited] (an action the
+    behaviour never draws keeps vv - eta lpol, as the sampled program leaves it); reach [S]: the probability that an episode visits the
+    state; length: sum_s reach, the expected number of slots per player and episode, E[N_P] / B; dv_tab [2S, 1], dlogit_tab [2S, A]: the
+    expectation of rnad_learn_fused_tabular's outputs with the batch normaliser replaced by its expectation, 2 w_v reach (v - target) / L
+    and reach * direction / L; linear bool [2S]: where dlogit_tab IS that expectation (both threshold gates open on every legal action,
+    a clip no sample can reach) -- elsewhere it is the gated, clipped direction at the expected q; target_bias [2]: the fp64 host sum of
+    reach * |target - v_target| per player."""
+
+    pi_processed: torch.Tensor
+    target: torch.Tensor
+    target_given_row: torch.Tensor
+    q: torch.Tensor
+    reach: torch.Tensor
+    length: float
+    dv_tab: torch.Tensor
+    dlogit_tab: torch.Tensor
+    linear: torch.Tensor
+    target_bias: torch.Tensor
+
+
+def _net_rows(tree, net):
+    """(logit [2S, A], v [2S]) of a net on the tree's 2S observations (the row player's S rows, then the column player's)."""
+    obs_row, obs_col = rnad_hip.observe_all(tree.handle(), tree.value_tensor.device)
+    was_training = net.training
+    net.eval()
+    with torch.no_grad():
+        halves = [net.forward_logits(obs) for obs in (obs_row, obs_col)]
+    net.train(was_training)
+    return (torch.cat([h[0] for h in halves], dim=0).float().contiguous(), torch.cat([h[1].reshape(-1) for h in halves], dim=0).float().contiguous())
+
+
+def _rows(tree, x, what, value=False):
+    """A row table [2S, A] (value: [2S]) on the tree's device from a tensor or a net."""
+    S, A = tree.value_tensor.shape[0], tree.max_actions
+    if not torch.is_tensor(x):
+        return _net_rows(tree, x)[1 if value else 0]
+    t = x.detach().to(device=tree.value_tensor.device, dtype=torch.float)
+    if value:
+        t = t.reshape(-1)
+    if tuple(t.shape) != ((2 * S,) if value else (2 * S, A)):
+        raise ValueError(f"expected_update: {what} must be a net or a row table {[2 * S] if value else [2 * S, A]}, got {tuple(x.shape)}")
+    return t.contiguous()
+
+
+def _sides(x, S):
+    """A row table [2S, k] as one member of the sweeps' layout, [S, 1, 2k]."""
+    x = x.reshape(2 * S, -1)
+    return torch.cat([x[:S], x[S:]], dim=1)[:, None, :].contiguous()
+
+
+def _sample_bound(tree, mu, pip, lpol, vv, hp, seen) -> float:
+    """An upper bound on |q| of any sampled slot, from maxima over the visited rows: with D the longest episode in states, cs <= K,
+    |e| <= E, |vv| <= V, |r| <= R a sampled target obeys |vt| <= V + rho (eta E (1 + g) + g R + g g V + V) + lambda c g g (|vt below| + V),
+    D times from 0; a tail is at most g (eta E + K R) + g g K |vt| + V, and |q| <= V + eta max|lpol| + tail / min mu."""
+    rows = torch.cat([seen, seen])
+    mu, pip, lpol, vv = (t.double()[rows] for t in (mu, pip, lpol, vv))
+    drawn = mu > 0
+    if not bool(drawn.any()):
+        return 0.0
+    K = float((pip[drawn] / mu[drawn]).max())
+    E = float((pip * torch.where(pip > 0, lpol, torch.zeros_like(lpol))).sum(-1).abs().max())
+    V, R = float(vv.abs().max()), float(tree.value_tensor.abs().max())
+    index, chance = tree.index_tensor, tree.chance_tensor
+    live = (index != 0) & (chance > 0)
+    frontier, D = torch.ones((1,), dtype=torch.long, device=index.device), 0
+    while frontier.numel() > 0:
+        D += 1
+        frontier = index[frontier][live[frontier]].to(torch.long)
+    g, vt = hp.gamma, 0.0
+    for _ in range(D):
+        vt = V + hp.rho * (hp.eta * E * (1 + g) + g * R + g * g * V + V) + abs(hp.lambda_) * hp.c * g * g * (vt + V)
+    tail = g * (hp.eta * E + K * R) + g * g * K * vt + V
+    return V + hp.eta * float(torch.where(drawn, lpol, torch.zeros_like(lpol)).abs().max()) + tail / float(mu[drawn].min())
+
+
+def expected_update(tree, behaviour, logit, v, v_target, logit_reg, logit_reg_, hp) -> ExpectedUpdate:
+    """The learner's update with the sampling taken out (rnad_vtrace_expect, csrc/vtrace_expect.hip): the expectation, over complete
+    episodes played by `behaviour` and the tree's chance, of the two-player V-trace targets and action values that RNaD's learner
+    computes from sampled trajectories, and of the row gradients it hands to the nets.  Every input is a net or a row table in the
+    learner's layout: behaviour a net (its raw policy) or a probability table [2S, A]; logit [2S, A] and v [2S] (a net given as `logit`
+    serves both when v is None); v_target [2S] (the target net's value head); logit_reg, logit_reg_ [2S, A].  hp: an
+    rnad_hip.LearnParams (make_learn_params).  pi, pi_processed and the log policies come from the learner's own policy-head and
+    process_policy kernels.  Refuses a behaviour that never draws an action the evaluated policy plays at a state it reaches: the
+    importance ratio there is infinite."""
+    from learn import tabular
+    from util import metric
+
+    if not metric.index_is_tree(tree):
+        raise ValueError("expected_update: the index tensor is not a tree: a state with two parents has no single expectation")
+    S, A = tree.value_tensor.shape[0], tree.max_actions
+    if v is None and not torch.is_tensor(logit):
+        logit_tab, v_tab = _net_rows(tree, logit)
+    else:
+        logit_tab, v_tab = _rows(tree, logit, "logit"), _rows(tree, v, "v", value=True)
+    vv = _rows(tree, v_target, "v_target", value=True)
+    on = tabular.legal_mask(tree)
+    legal = torch.cat([on[:, :A], on[:, A:]], dim=0).float().contiguous()
+    zero = torch.zeros_like(logit_tab)
+    pi, log_pi = rnad_hip.policy_head(logit_tab, mask=legal, want_log=True)
+    pip = rnad_hip.process_policy(pi, legal, hp.n_disc, hp.eps_threshold)
+    magnet = zero
+    for weight, reg in ((hp.alpha, logit_reg), (hp.one_minus_alpha, logit_reg_)):
+        if weight != 0:  # a term whose weight is exactly zero is skipped, as train_step skips it
+            log_reg = rnad_hip.policy_head(_rows(tree, reg, "logit_reg"), mask=legal, want_log=True)[1]
+            magnet = magnet + weight * torch.where(legal > 0, log_reg, zero)
+    lpol = torch.where(legal > 0, torch.where(legal > 0, log_pi, zero) - magnet, zero)
+    if torch.is_tensor(behaviour):
+        mu = _rows(tree, behaviour, "behaviour")
+    else:
+        mu = rnad_hip.policy_head(_net_rows(tree, behaviour)[0], mask=legal)
+    if not bool(torch.isfinite(mu).all()) or bool((mu < 0).any()):
+        raise ValueError("expected_update: the behaviour table must be finite and nonnegative")
+    hyper = [(hp.eta, hp.gamma, hp.lambda_, hp.rho, hp.c)]
+    target, given_row, q, reach = rnad_hip.vtrace_expect(tree.handle(), hyper, _sides(mu, S), _sides(pip, S), _sides(lpol, S), _sides(vv, S))
+    reach = reach[:, 0]
+    reach2 = torch.cat([reach, reach])
+    never = (pip > 0) & (mu == 0) & (reach2 > 0)[:, None]
+    if bool(never.any().item()):
+        row, a = (int(x) for x in never.nonzero()[0])
+        raise ValueError(f"expected_update: the behaviour never draws action {a} of player {row // S} at state {row % S}, which the "
+                         f"evaluated policy plays with probability {pip[row, a].item():.3g}: the importance ratio is infinite")
+    target = torch.cat([target[:, 0, 0], target[:, 0, 1]])
+    q = torch.cat([q[:, 0, :A], q[:, 0, A:]], dim=0)
+    L = float(reach.double().sum())
+    dv_tab = (2 * hp.w_v * reach2.double() * (v_tab.double() - target.double()) / L).float()[:, None]
+    # the row gradient of one slot at the expected q (vtrace.py:396-431 in closed form): gates and clip applied to it
+    adv = (q - (pip * q).sum(-1, keepdim=True)).clamp(-hp.clip, hp.clip)
+    l = logit_tab - (logit_tab * legal).sum(-1, keepdim=True) / A
+    lo, hi = l > -hp.threshold, l < hp.threshold
+    force = legal * (torch.where(lo, adv.clamp(max=0), zero) + torch.where(hi, adv.clamp(min=0), zero))
+    grad = force - legal * force.sum(-1, keepdim=True) / A
+    dlogit_tab = (reach2.double()[:, None] * (-hp.w_n * grad.double()) / L).float()
+    gates_open = ((lo & hi) | (legal == 0)).all(dim=-1)
+    bound = _sample_bound(tree, mu, pip, lpol, vv, hp, reach > 0)
+    linear = gates_open & (reach2 > 0) & bool(2 * bound <= hp.clip)
+    bias = reach2.double() * (target.double() - vv.double()).abs()
+    target_bias = torch.stack([bias[:S].sum(), bias[S:].sum()]).cpu()
+    return ExpectedUpdate(pip, target, given_row[:, 0], q, reach, L, dv_tab, dlogit_tab, linear, target_bias)

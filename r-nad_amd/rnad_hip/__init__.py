@@ -2083,6 +2083,72 @@ def reg_evaluate(tree, eta, policies, log_reg, values=None, q=None, residual=Non
     return tuple(outs)
 
 
+def vtrace_expect(tree, hyper, mu, pip, lpol, vv, target=None, target_given_row=None, q=None, reach=None, workspace=None):
+    """rnad_vtrace_expect: the exact expected learner update of n members.  mu (the behaviour), pip (pi_processed), lpol (log_pi minus the
+    mixed log magnets) f32 [S, n, 2A] in the layout of cross_play's policies, vv f32 [S, n, 2] (the target net's value per side), hyper: n
+    rows (eta, gamma, lambda, rho, c) on the host (or one row for all) -> (target [S, n, 2]: the expected V-trace target of each side's
+    row given that it is visited, target_given_row [S, n, A]: the column side's given the row action taken, q [S, n, 2A]: the expected
+    action values, reach [S, n]: best_response's joint reach of the table mu, bit for bit).  The four outputs and the workspace (f32,
+    rnad_vtrace_expect_workspace(S, A, n) floats) may be given as existing buffers (every output row is written).  With all five given
+    nothing is allocated on the device: capturable, and a captured call keeps the hyperparameters it was captured with."""
+    if not torch.is_tensor(mu) or mu.dim() != 3:
+        raise RnadHipError("vtrace_expect: mu must be a tensor of shape [S, n, 2A]")
+    mp = _dp(mu, F32, "mu")
+    if not isinstance(tree, TreeHandle):
+        raise RnadHipError("vtrace_expect: tree must be a TreeHandle (Tree.handle())")
+    S, n, A2 = mu.shape
+    if S != tree.S or A2 != 2 * tree.A:
+        raise RnadHipError(f"vtrace_expect: mu of shape {tuple(mu.shape)} does not fit a tree of {tree.S} states and {tree.A} actions "
+                           f"(expected [{tree.S}, n, {2 * tree.A}])")
+    if S < 2:
+        raise RnadHipError(f"vtrace_expect: a tree of {S} states has no root")
+    if lib().rnad_vtrace_expect_size(S, n) < 0:
+        raise RnadHipError(f"vtrace_expect: {n} members outside [1, {CROSS_PLAY_MAX}]")
+    if mu.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
+        raise RnadHipError(f"vtrace_expect: mu lives on {mu.device}, the tree's tables on {tree.device}")
+    inputs, in_ptrs = [("mu", mu)], [mp]
+    for name, t, shape in (("pip", pip, (S, n, A2)), ("lpol", lpol, (S, n, A2)), ("vv", vv, (S, n, 2))):
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"vtrace_expect: {name} must be a tensor of shape {list(shape)}")
+        in_ptrs.append(_dp(t, F32, name))
+        if tuple(t.shape) != shape or t.device != mu.device:
+            raise RnadHipError(f"vtrace_expect: {name} must be {list(shape)} on {mu.device}, got {list(t.shape)} on {t.device}")
+        inputs.append((name, t))
+    rows = hyper.tolist() if torch.is_tensor(hyper) else list(hyper)
+    if rows and not hasattr(rows[0], "__len__"):
+        rows = [rows] * n
+    rows = [[float(x) for x in row] for row in rows]
+    if len(rows) != n or any(len(row) != 5 for row in rows):
+        raise RnadHipError(f"vtrace_expect: hyper must hold {n} rows (eta, gamma, lambda, rho, c), or one row for all")
+    finite = lambda x: x == x and abs(x) != float("inf")  # noqa: E731
+    for k, (eta, gamma, lambda_, rho, c) in enumerate(rows):
+        if not (gamma > 0 and finite(gamma)):
+            raise RnadHipError(f"vtrace_expect: gamma[{k}] = {gamma} is not a positive number")
+        if not (rho >= 0 and c >= 0):
+            raise RnadHipError(f"vtrace_expect: the clips rho[{k}] = {rho}, c[{k}] = {c} must not be negative")
+        if not (finite(eta) and finite(lambda_)):
+            raise RnadHipError(f"vtrace_expect: eta[{k}] = {eta} or lambda[{k}] = {lambda_} is not finite")
+    A = tree.A
+    outs, ptrs = [], []
+    names = ("target", "target_given_row", "q", "reach", "workspace")
+    for name, given, shape in (("target", target, (S, n, 2)), ("target_given_row", target_given_row, (S, n, A)), ("q", q, (S, n, A2)),
+                               ("reach", reach, (S, n)), ("workspace", workspace, (lib().rnad_vtrace_expect_workspace(S, A, n),))):
+        t = torch.empty(shape, dtype=F32, device=mu.device) if given is None else given
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"vtrace_expect: {name} must be a tensor of shape {list(shape)}")
+        ptrs.append(_dp(t, F32, name))
+        if tuple(t.shape) != shape or t.device != mu.device:
+            raise RnadHipError(f"vtrace_expect: {name} must be {list(shape)} on {mu.device}, got {list(t.shape)} on {t.device}")
+        for other_name, other in inputs + list(zip(names, outs)):
+            lo, hi = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
+            if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+                raise RnadHipError(f"vtrace_expect: {name} aliases {other_name} (the buffers overlap)")
+        outs.append(t)
+    hyper_c = (C.c_float * (5 * n))(*[x for row in rows for x in row])
+    _check(lib().rnad_vtrace_expect(tree.ptr, n, C.cast(hyper_c, C.c_void_p), *in_ptrs, *ptrs, _stream()))
+    return tuple(outs[:4])
+
+
 # --------------------------------------------------------------------------------------- host-side: generator / solver
 def solve_matrix(M, max_actions):
     """tree.py:199-234 for one fp32 matrix (CPU tensor [ra, ca]) -> (solution [2*max_actions], value)."""
