@@ -964,7 +964,7 @@ int rnad_reg_evaluate(const rnad_tree_t *tree, int n, const float *eta, const fl
  * [S][n][2] (device).  Outputs (device), all required and the caller's: target f32 [S][n][2],
  * target_given_row f32 [S][n][A], q f32 [S][n][2A], reach f32 [S][n]; workspace: f32,
  * rnad_vtrace_expect_workspace(S, A, n) = S * n * (3A + 5) floats, in which every state leaves one
- * record for its parent (its contents after the call are unspecified).  Every row is written --
+ * record for its parent (rnad_vtrace_moments, below, states its layout and reads it).  Every row is written --
  * state 0 and states no live path reaches with zeros.  One launch that writes those rows and the
  * root's reach, one per level bottom-up, one per level top-down, on `stream`; nothing is allocated,
  * no atomics, a fixed order of operations: the same inputs give the same bits and the call can be
@@ -980,6 +980,52 @@ int64_t rnad_vtrace_expect_size(int64_t S, int n);
 int64_t rnad_vtrace_expect_workspace(int64_t S, int A, int n);
 int rnad_vtrace_expect(const rnad_tree_t *tree, int n, const float *hyper, const float *mu, const float *pip, const float *lpol,
                        const float *vv, float *target, float *target_given_row, float *q, float *reach, float *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Exact variance of the learner update  --  no counterpart in the reference.  The second central
+ * moments of what rnad_vtrace_expect gives in expectation: over the complete episodes that visit a
+ * (player, state) row, of the sampled V-trace target and of every entry of the sampled q.  Runs
+ * AFTER a completed rnad_vtrace_expect on the same tree, n, hyper, mu, pip, lpol and vv, and takes
+ * every first moment from that call: its outputs target, target_given_row, q and its workspace,
+ * which after the call holds one export record per state, field-major [S][3A + 5][n]:
+ *   0 vv0   1 W0   2 e0   3 vv1   4 sum_a pip0[a] W1[a]   5 .. mu0[A]   5 + A .. cs0[A]
+ *   5 + 2A .. (W1 - vv1)[A]                (zeros for state 0 and states no live path reaches)
+ * With d0 = W0 - vv0, dW1[a] = W1[a] - vv1 and the notation of rnad_vtrace_expect, bottom-up:
+ *   V0[s]    = sum_{a,b} mu0[a] mu1[b] sum_t p (dev^2 + (u ? (l g g min(w, c))^2 V0[u] : 0)),
+ *              dev  = min(w, rho) (g eta e1 - eta e0 - vv0 + g (u ? g vv0[u] : r))
+ *                     + (u ? l g g min(w, c) d0[u] : 0) - d0[s]
+ *   V1[s][a] = sum_b mu1[b] sum_t p (u ? sum_a' mu0[u][a'] (dev'^2 + (l g g min(w', c))^2 V1[u][a'])
+ *                                      : (min(cs1[b], rho) (-r - eta e1 - vv1) - dW1[s][a])^2),
+ *              dev' = min(w', rho) (g eta e0[u] - eta e1 + g g vv1[u] - vv1)
+ *                     + l g g min(w', c) dW1[u][a'] - dW1[s][a];      V1[s][a] = 0 where mu0[a] = 0
+ *   target_var[0] = V0,  target_given_row_var = V1,
+ *   target_var[1] = sum_a mu0[a] (V1[a] + (W1[a] - target[1])^2)
+ *   q_var[0][a] = (sum_b mu1[b] sum_t p ((tm - tbar)^2 + (u ? (g g cs1[b])^2 V0[u] : 0))
+ *                  + (1 - mu0[a]) tbar^2) / mu0[a],
+ *              tm = g eta e1 + g cs1[b] (u ? g W0[u] : r) - vv0,  tbar = q[0][a] - (vv0 - eta lpol0[a])
+ *   q_var[1][b] = (sum_a mu0[a] sum_t p (u ? sum_a' mu0[u][a'] ((tm - tbar)^2 + (g g cs0[u][a'])^2 V1[u][a'])
+ *                                          : (tm - tbar)^2) + (1 - mu1[b]) tbar^2) / mu1[b],
+ *              tm = (u ? g eta e0[u] + g g cs0[u][a'] W1[u][a'] : -r) - vv1,
+ *              tbar = q[1][b] - (vv1 - eta lpol1[b]);                  q_var = 0 where mu = 0
+ * Every summand is a square or a product of squares; nothing is formed as E[x^2] - E[x]^2.
+ * Inputs (device, read only): mu, pip, lpol f32 [S][n][2A], vv f32 [S][n][2], expect_workspace,
+ * target f32 [S][n][2], target_given_row f32 [S][n][A], q f32 [S][n][2A]; hyper: HOST array [n][5]
+ * whose values travel as kernel arguments.  Outputs (device), all required and the caller's:
+ * target_var f32 [S][n][2], target_given_row_var f32 [S][n][A], q_var f32 [S][n][2A]; workspace:
+ * f32, rnad_vtrace_moments_workspace(S, A, n) = S * n * (A + 1) floats, in which every state leaves
+ * V0 | V1[A] for its parent, field-major [S][A + 1][n].  Every row is written -- state 0 and states
+ * no live path reaches with zeros.  One launch that writes those rows, one per level bottom-up, on
+ * `stream`; nothing is allocated, no atomics, a fixed order of operations: the same inputs give the
+ * same bits and the call can be captured in a hipGraph.  Refused on the host, before anything is
+ * written: what rnad_vtrace_expect refuses, and an expect_workspace (or any other input) that
+ * overlaps an output.
+ * rnad_vtrace_moments_workspace (host only): -1 unless S >= 2, 1 <= n <= RNAD_CROSS_PLAY_MAX and
+ * 1 <= A <= RNAD_MAX_ACTIONS.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t rnad_vtrace_moments_workspace(int64_t S, int A, int n);
+int rnad_vtrace_moments(const rnad_tree_t *tree, int n, const float *hyper, const float *mu, const float *pip, const float *lpol,
+                        const float *vv, const float *expect_workspace, const float *target, const float *target_given_row,
+                        const float *q, float *target_var, float *target_given_row_var, float *q_var, float *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Native tree generator (HOST code)  --  environment/tree.py:164-366 (generate, _transition_probs,

@@ -502,18 +502,29 @@ class RNaD:
         under the actor, and the expected row gradients of the value and policy heads."""
         from learn import vtrace
 
+        return vtrace.expected_update(*self._whole_tree_update_args("expected_update", alpha))
+
+    def update_noise(self, alpha=None):
+        """The twin of expected_update: learn.vtrace.update_noise of the same nets, hyperparameters and behaviour -- the exact variance of
+        the sampled V-trace targets and action values per (player, state) row next to their expectation (UpdateNoise.expected), the
+        one-episode variance of the value head's row gradients and the batch at which their signal equals their noise."""
+        from learn import vtrace
+
+        return vtrace.update_noise(*self._whole_tree_update_args("update_noise", alpha))
+
+    def _whole_tree_update_args(self, what, alpha):
+        """The arguments of learn.vtrace.expected_update and update_noise for this trainer's nets."""
         if self.net is None or self.net_target is None or self.net_reg is None or self.net_reg_ is None:
-            raise ValueError("expected_update: this trainer is not initialised")
+            raise ValueError(f"{what}: this trainer is not initialised")
         if alpha is None:
             delta_m = self._steps_of_current_update()
             if delta_m is None:
-                raise ValueError("expected_update: training is over: the schedule has no alpha for this m; pass alpha")
+                raise ValueError(f"{what}: training is over: the schedule has no alpha for this m; pass alpha")
             alpha = self.alpha_of(self.n, delta_m)
         alpha = float(alpha)
         if not 0 <= alpha <= 1:
-            raise ValueError(f"expected_update: alpha = {alpha} outside [0, 1]")
-        return vtrace.expected_update(self.tree, self.net, self.net, None, self.net_target, self.net_reg, self.net_reg_,
-                                      self._learn_params(alpha))
+            raise ValueError(f"{what}: alpha = {alpha} outside [0, 1]")
+        return self.tree, self.net, self.net, None, self.net_target, self.net_reg, self.net_reg_, self._learn_params(alpha)
 
     def _grad_bucket(self, weights):
         """One flat fp32 buffer holding the learner's gradients back to back (the RCCL bucket) and per-tensor views of it."""

@@ -229,6 +229,12 @@ def expected_update(tree, behaviour, logit, v, v_target, logit_reg, logit_reg_, 
     rnad_hip.LearnParams (make_learn_params).  pi, pi_processed and the log policies come from the learner's own policy-head and
     process_policy kernels.  Refuses a behaviour that never draws an action the evaluated policy plays at a state it reaches: the
     importance ratio there is infinite."""
+    return _expected(tree, behaviour, logit, v, v_target, logit_reg, logit_reg_, hp)[0]
+
+
+def _expected(tree, behaviour, logit, v, v_target, logit_reg, logit_reg_, hp):
+    """expected_update's result and what update_noise needs of the sweep behind it: (hyper, the four inputs in the sweep's layout, the
+    export workspace, the sweep's raw outputs, v as a row table)."""
     from learn import tabular
     from util import metric
 
@@ -258,7 +264,10 @@ def expected_update(tree, behaviour, logit, v, v_target, logit_reg, logit_reg_, 
     if not bool(torch.isfinite(mu).all()) or bool((mu < 0).any()):
         raise ValueError("expected_update: the behaviour table must be finite and nonnegative")
     hyper = [(hp.eta, hp.gamma, hp.lambda_, hp.rho, hp.c)]
-    target, given_row, q, reach = rnad_hip.vtrace_expect(tree.handle(), hyper, _sides(mu, S), _sides(pip, S), _sides(lpol, S), _sides(vv, S))
+    sides = tuple(_sides(t, S) for t in (mu, pip, lpol, vv))
+    workspace = torch.empty((rnad_hip.lib().rnad_vtrace_expect_workspace(S, A, 1),), dtype=torch.float, device=mu.device)
+    first = rnad_hip.vtrace_expect(tree.handle(), hyper, *sides, workspace=workspace)
+    target, given_row, q, reach = first
     reach = reach[:, 0]
     reach2 = torch.cat([reach, reach])
     never = (pip > 0) & (mu == 0) & (reach2 > 0)[:, None]
@@ -282,4 +291,48 @@ def expected_update(tree, behaviour, logit, v, v_target, logit_reg, logit_reg_, 
     linear = gates_open & (reach2 > 0) & bool(2 * bound <= hp.clip)
     bias = reach2.double() * (target.double() - vv.double()).abs()
     target_bias = torch.stack([bias[:S].sum(), bias[S:].sum()]).cpu()
-    return ExpectedUpdate(pip, target, given_row[:, 0], q, reach, L, dv_tab, dlogit_tab, linear, target_bias)
+    return ExpectedUpdate(pip, target, given_row[:, 0], q, reach, L, dv_tab, dlogit_tab, linear, target_bias), (hyper, sides, workspace, first, v_tab)
+
+
+# ---------------------------------------------------------------------------------------------------- the exact variance of the update
+class UpdateNoise(NamedTuple):
+    """update_noise's result: the variance, over complete episodes played by the behaviour, of what ExpectedUpdate gives in expectation;
+    rows in the learner's layout (row = player * S + state), tensors on the tree's device unless said otherwise.
+    expected: the ExpectedUpdate of the same call; target_var [2S]: Var[v_target at the slot | the row is visited]; target_given_row_var
+    [S, A]: the column player's given the row action taken (0 where the behaviour never draws it); q_var [2S, A]: the variance of every
+    entry of the sampled q, drawn or not (0 where mu = 0) -- the input to the variance of dlogit, which is not derived where the threshold
+    gates or the NeuRD clip are non-linear.  For ONE episode (a batch of B divides by B), fp64 on the host: dv_var_tab [2S]: the variance
+    of the row's entry of dv_tab, (2 w_v / L)^2 (reach (var + d^2) - reach^2 d^2) with d = v - target and the normaliser at its
+    expectation L; target_noise [2]: sum_s reach target_var per player, to be read next to target_bias; episodes_for_unit_snr [2]:
+    sum_rows dv_var_tab / sum_rows dv_tab^2, the batch at which the value head's gradient has signal equal to noise (inf where the
+    signal is 0)."""
+
+    expected: ExpectedUpdate
+    target_var: torch.Tensor
+    target_given_row_var: torch.Tensor
+    q_var: torch.Tensor
+    dv_var_tab: torch.Tensor
+    target_noise: torch.Tensor
+    episodes_for_unit_snr: torch.Tensor
+
+
+def update_noise(tree, behaviour, logit, v, v_target, logit_reg, logit_reg_, hp) -> UpdateNoise:
+    """The noise of the learner's update next to its expectation (rnad_vtrace_moments, csrc/vtrace_moments.hip): the exact second central
+    moments of the sampled V-trace targets and action values, by a second bottom-up sweep over the first moments expected_update's sweep
+    left.  Arguments and refusals are expected_update's."""
+    expected, (hyper, sides, workspace, first, v_tab) = _expected(tree, behaviour, logit, v, v_target, logit_reg, logit_reg_, hp)
+    S, A = tree.value_tensor.shape[0], tree.max_actions
+    target_var, given_row_var, q_var = rnad_hip.vtrace_moments(tree.handle(), hyper, *sides, workspace, *first[:3])
+    target_var = torch.cat([target_var[:, 0, 0], target_var[:, 0, 1]])
+    q_var = torch.cat([q_var[:, 0, :A], q_var[:, 0, A:]], dim=0)
+    reach2 = torch.cat([expected.reach, expected.reach]).double()
+    L = expected.length
+    d = v_tab.double() - expected.target.double()
+    var = target_var.double()
+    dv_var_tab = (2 * hp.w_v / L) ** 2 * (reach2 * (var + d * d) - reach2 * reach2 * d * d)
+    noise = reach2 * var
+    target_noise = torch.stack([noise[:S].sum(), noise[S:].sum()]).cpu()
+    signal = (2 * hp.w_v * reach2 * d / L) ** 2
+    inf = torch.full((), float("inf"), dtype=torch.double, device=signal.device)
+    snr = [torch.where(signal[r].sum() > 0, dv_var_tab[r].sum() / signal[r].sum(), inf) for r in (slice(0, S), slice(S, 2 * S))]
+    return UpdateNoise(expected, target_var, given_row_var[:, 0], q_var, dv_var_tab, target_noise, torch.stack(snr).cpu())

@@ -2083,6 +2083,68 @@ def reg_evaluate(tree, eta, policies, log_reg, values=None, q=None, residual=Non
     return tuple(outs)
 
 
+def _vtrace_inputs(what, tree, hyper, mu, pip, lpol, vv):
+    """The argument checks rnad_vtrace_expect and rnad_vtrace_moments share -> (S, n, A, [(name, tensor)], [pointers], hyper as C floats)."""
+    if not torch.is_tensor(mu) or mu.dim() != 3:
+        raise RnadHipError(f"{what}: mu must be a tensor of shape [S, n, 2A]")
+    mp = _dp(mu, F32, "mu")
+    if not isinstance(tree, TreeHandle):
+        raise RnadHipError(f"{what}: tree must be a TreeHandle (Tree.handle())")
+    S, n, A2 = mu.shape
+    if S != tree.S or A2 != 2 * tree.A:
+        raise RnadHipError(f"{what}: mu of shape {tuple(mu.shape)} does not fit a tree of {tree.S} states and {tree.A} actions "
+                           f"(expected [{tree.S}, n, {2 * tree.A}])")
+    if S < 2:
+        raise RnadHipError(f"{what}: a tree of {S} states has no root")
+    if lib().rnad_vtrace_expect_size(S, n) < 0:
+        raise RnadHipError(f"{what}: {n} members outside [1, {CROSS_PLAY_MAX}]")
+    if mu.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
+        raise RnadHipError(f"{what}: mu lives on {mu.device}, the tree's tables on {tree.device}")
+    inputs, in_ptrs = [("mu", mu)], [mp]
+    for name, t, shape in (("pip", pip, (S, n, A2)), ("lpol", lpol, (S, n, A2)), ("vv", vv, (S, n, 2))):
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"{what}: {name} must be a tensor of shape {list(shape)}")
+        in_ptrs.append(_dp(t, F32, name))
+        if tuple(t.shape) != shape or t.device != mu.device:
+            raise RnadHipError(f"{what}: {name} must be {list(shape)} on {mu.device}, got {list(t.shape)} on {t.device}")
+        inputs.append((name, t))
+    rows = hyper.tolist() if torch.is_tensor(hyper) else list(hyper)
+    if rows and not hasattr(rows[0], "__len__"):
+        rows = [rows] * n
+    rows = [[float(x) for x in row] for row in rows]
+    if len(rows) != n or any(len(row) != 5 for row in rows):
+        raise RnadHipError(f"{what}: hyper must hold {n} rows (eta, gamma, lambda, rho, c), or one row for all")
+    finite = lambda x: x == x and abs(x) != float("inf")  # noqa: E731
+    for k, (eta, gamma, lambda_, rho, c) in enumerate(rows):
+        if not (gamma > 0 and finite(gamma)):
+            raise RnadHipError(f"{what}: gamma[{k}] = {gamma} is not a positive number")
+        if not (rho >= 0 and c >= 0):
+            raise RnadHipError(f"{what}: the clips rho[{k}] = {rho}, c[{k}] = {c} must not be negative")
+        if not (finite(eta) and finite(lambda_)):
+            raise RnadHipError(f"{what}: eta[{k}] = {eta} or lambda[{k}] = {lambda_} is not finite")
+    hyper_c = (C.c_float * (5 * n))(*[x for row in rows for x in row])
+    return S, n, tree.A, inputs, in_ptrs, hyper_c
+
+
+def _vtrace_buffers(what, device, specs, inputs):
+    """Output buffers (name, given or None, shape) of a sweep: allocated where not given, checked against `inputs` [(name, tensor)] and
+    each other for overlap -> (tensors, pointers)."""
+    outs, ptrs, names = [], [], [name for name, _, _ in specs]
+    for name, given, shape in specs:
+        t = torch.empty(shape, dtype=F32, device=device) if given is None else given
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"{what}: {name} must be a tensor of shape {list(shape)}")
+        ptrs.append(_dp(t, F32, name))
+        if tuple(t.shape) != tuple(shape) or t.device != device:
+            raise RnadHipError(f"{what}: {name} must be {list(shape)} on {device}, got {list(t.shape)} on {t.device}")
+        for other_name, other in inputs + list(zip(names, outs)):
+            lo, hi = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
+            if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+                raise RnadHipError(f"{what}: {name} aliases {other_name} (the buffers overlap)")
+        outs.append(t)
+    return outs, ptrs
+
+
 def vtrace_expect(tree, hyper, mu, pip, lpol, vv, target=None, target_given_row=None, q=None, reach=None, workspace=None):
     """rnad_vtrace_expect: the exact expected learner update of n members.  mu (the behaviour), pip (pi_processed), lpol (log_pi minus the
     mixed log magnets) f32 [S, n, 2A] in the layout of cross_play's policies, vv f32 [S, n, 2] (the target net's value per side), hyper: n
@@ -2091,62 +2153,38 @@ def vtrace_expect(tree, hyper, mu, pip, lpol, vv, target=None, target_given_row=
     action values, reach [S, n]: best_response's joint reach of the table mu, bit for bit).  The four outputs and the workspace (f32,
     rnad_vtrace_expect_workspace(S, A, n) floats) may be given as existing buffers (every output row is written).  With all five given
     nothing is allocated on the device: capturable, and a captured call keeps the hyperparameters it was captured with."""
-    if not torch.is_tensor(mu) or mu.dim() != 3:
-        raise RnadHipError("vtrace_expect: mu must be a tensor of shape [S, n, 2A]")
-    mp = _dp(mu, F32, "mu")
-    if not isinstance(tree, TreeHandle):
-        raise RnadHipError("vtrace_expect: tree must be a TreeHandle (Tree.handle())")
-    S, n, A2 = mu.shape
-    if S != tree.S or A2 != 2 * tree.A:
-        raise RnadHipError(f"vtrace_expect: mu of shape {tuple(mu.shape)} does not fit a tree of {tree.S} states and {tree.A} actions "
-                           f"(expected [{tree.S}, n, {2 * tree.A}])")
-    if S < 2:
-        raise RnadHipError(f"vtrace_expect: a tree of {S} states has no root")
-    if lib().rnad_vtrace_expect_size(S, n) < 0:
-        raise RnadHipError(f"vtrace_expect: {n} members outside [1, {CROSS_PLAY_MAX}]")
-    if mu.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
-        raise RnadHipError(f"vtrace_expect: mu lives on {mu.device}, the tree's tables on {tree.device}")
-    inputs, in_ptrs = [("mu", mu)], [mp]
-    for name, t, shape in (("pip", pip, (S, n, A2)), ("lpol", lpol, (S, n, A2)), ("vv", vv, (S, n, 2))):
-        if not torch.is_tensor(t):
-            raise RnadHipError(f"vtrace_expect: {name} must be a tensor of shape {list(shape)}")
-        in_ptrs.append(_dp(t, F32, name))
-        if tuple(t.shape) != shape or t.device != mu.device:
-            raise RnadHipError(f"vtrace_expect: {name} must be {list(shape)} on {mu.device}, got {list(t.shape)} on {t.device}")
-        inputs.append((name, t))
-    rows = hyper.tolist() if torch.is_tensor(hyper) else list(hyper)
-    if rows and not hasattr(rows[0], "__len__"):
-        rows = [rows] * n
-    rows = [[float(x) for x in row] for row in rows]
-    if len(rows) != n or any(len(row) != 5 for row in rows):
-        raise RnadHipError(f"vtrace_expect: hyper must hold {n} rows (eta, gamma, lambda, rho, c), or one row for all")
-    finite = lambda x: x == x and abs(x) != float("inf")  # noqa: E731
-    for k, (eta, gamma, lambda_, rho, c) in enumerate(rows):
-        if not (gamma > 0 and finite(gamma)):
-            raise RnadHipError(f"vtrace_expect: gamma[{k}] = {gamma} is not a positive number")
-        if not (rho >= 0 and c >= 0):
-            raise RnadHipError(f"vtrace_expect: the clips rho[{k}] = {rho}, c[{k}] = {c} must not be negative")
-        if not (finite(eta) and finite(lambda_)):
-            raise RnadHipError(f"vtrace_expect: eta[{k}] = {eta} or lambda[{k}] = {lambda_} is not finite")
-    A = tree.A
-    outs, ptrs = [], []
-    names = ("target", "target_given_row", "q", "reach", "workspace")
-    for name, given, shape in (("target", target, (S, n, 2)), ("target_given_row", target_given_row, (S, n, A)), ("q", q, (S, n, A2)),
-                               ("reach", reach, (S, n)), ("workspace", workspace, (lib().rnad_vtrace_expect_workspace(S, A, n),))):
-        t = torch.empty(shape, dtype=F32, device=mu.device) if given is None else given
-        if not torch.is_tensor(t):
-            raise RnadHipError(f"vtrace_expect: {name} must be a tensor of shape {list(shape)}")
-        ptrs.append(_dp(t, F32, name))
-        if tuple(t.shape) != shape or t.device != mu.device:
-            raise RnadHipError(f"vtrace_expect: {name} must be {list(shape)} on {mu.device}, got {list(t.shape)} on {t.device}")
-        for other_name, other in inputs + list(zip(names, outs)):
-            lo, hi = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
-            if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
-                raise RnadHipError(f"vtrace_expect: {name} aliases {other_name} (the buffers overlap)")
-        outs.append(t)
-    hyper_c = (C.c_float * (5 * n))(*[x for row in rows for x in row])
+    S, n, A, inputs, in_ptrs, hyper_c = _vtrace_inputs("vtrace_expect", tree, hyper, mu, pip, lpol, vv)
+    outs, ptrs = _vtrace_buffers("vtrace_expect", mu.device,
+                                 (("target", target, (S, n, 2)), ("target_given_row", target_given_row, (S, n, A)), ("q", q, (S, n, 2 * A)),
+                                  ("reach", reach, (S, n)), ("workspace", workspace, (lib().rnad_vtrace_expect_workspace(S, A, n),))), inputs)
     _check(lib().rnad_vtrace_expect(tree.ptr, n, C.cast(hyper_c, C.c_void_p), *in_ptrs, *ptrs, _stream()))
     return tuple(outs[:4])
+
+
+def vtrace_moments(tree, hyper, mu, pip, lpol, vv, expect_workspace, target, target_given_row, q, target_var=None,
+                   target_given_row_var=None, q_var=None, workspace=None):
+    """rnad_vtrace_moments: the exact variance of the learner's estimates of n members, after a completed vtrace_expect on the same tree,
+    hyper, mu, pip, lpol and vv, whose outputs target [S, n, 2], target_given_row [S, n, A], q [S, n, 2A] and workspace (expect_workspace,
+    rnad_vtrace_expect_workspace(S, A, n) floats) are this call's first moments -> (target_var [S, n, 2]: the variance of each side's
+    sampled V-trace target given that the row is visited, target_given_row_var [S, n, A]: the column side's given the row action taken
+    (0 where the behaviour never draws it), q_var [S, n, 2A]: the variance of every entry of the sampled q (0 where mu = 0)).  The three
+    outputs and the workspace (f32, rnad_vtrace_moments_workspace(S, A, n) floats) may be given as existing buffers (every output row is
+    written).  With all four given nothing is allocated on the device: capturable, with the hyperparameters it was captured with."""
+    S, n, A, inputs, in_ptrs, hyper_c = _vtrace_inputs("vtrace_moments", tree, hyper, mu, pip, lpol, vv)
+    for name, t, shape in (("expect_workspace", expect_workspace, (lib().rnad_vtrace_expect_workspace(S, A, n),)), ("target", target, (S, n, 2)),
+                           ("target_given_row", target_given_row, (S, n, A)), ("q", q, (S, n, 2 * A))):
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"vtrace_moments: {name} must be a tensor of shape {list(shape)}")
+        in_ptrs.append(_dp(t, F32, name))
+        if tuple(t.shape) != shape or t.device != mu.device:
+            raise RnadHipError(f"vtrace_moments: {name} must be {list(shape)} on {mu.device}, got {list(t.shape)} on {t.device}")
+        inputs.append((name, t))
+    outs, ptrs = _vtrace_buffers("vtrace_moments", mu.device,
+                                 (("target_var", target_var, (S, n, 2)), ("target_given_row_var", target_given_row_var, (S, n, A)),
+                                  ("q_var", q_var, (S, n, 2 * A)), ("workspace", workspace, (lib().rnad_vtrace_moments_workspace(S, A, n),))),
+                                 inputs)
+    _check(lib().rnad_vtrace_moments(tree.ptr, n, C.cast(hyper_c, C.c_void_p), *in_ptrs, *ptrs, _stream()))
+    return tuple(outs[:3])
 
 
 # --------------------------------------------------------------------------------------- host-side: generator / solver
