@@ -636,7 +636,25 @@ int rnad_bucket_records(const rnad_tree_t *tree, const float *logit_tab, const f
                         const float *logit_reg_tab, const float *logit_reg_tab_, const rnad_learn_params_t *hp,
                         const rnad_step_params_t *device_params, float *records, float *fast_records, float *policy_rows,
                         const int32_t *rows, const int64_t *n_rows, void *stream);
-/* Distinct observations (csrc/rows_dedup.hip).  What a net contributes to a (player, state) row is a function of the row's observation
+/* rnad_bucket_behaviour_records (csrc/replay.hip): the fast records of a compact batch that was played by an OLDER net.  The learner
+ * (fast_slot) reads the acting policy mu of a slot in two column blocks of its row's fast record only -- cs = pi_processed / mu and
+ * inv_mu = 1 / mu, learn/vtrace.py:199-204 -- which rnad_bucket_records fills with the actor's own pi.  Here they are rebuilt from the
+ * policy rows the batch was played with, so rnad_learn_bucketed_compact on the result is the off-policy update of that batch:
+ *   fast_records   this step's on-policy table, [2S][rnad_bucket_fast_record_stride(A)], read once;
+ *   mu_rows[k]     the policy rows of behaviour k, [2S][rnad_bucket_policy_row_stride(A)] -- the floats its rollout sampled from;
+ *   out[k]         a whole fast-record table for behaviour k:
+ *                    floats 0 .. 4 + 2A - 1    the input's bits (v | v_target | e0 | gate bits | pi_processed[A] | elp[A])
+ *                    out[k][r][4 + 2A + a]     fast_records[r][4 + a] / mu_rows[k][r][a]
+ *                    out[k][r][4 + 3A + a]     1.0f / mu_rows[k][r][a]
+ * mu_rows / out are HOST arrays of n device pointers, 1 <= n <= RNAD_BEHAVIOUR_MAX; they travel by value in the kernel arguments.  IEEE fp32
+ * divisions, those of rnad_bucket_records: mu_rows[k] = the actor's own policy rows gives the input's bits.  A column with mu = 0 (an
+ * illegal action) holds inf or NaN, as the on-policy record does; the learner selects by the action taken.  rows / n_rows as in
+ * rnad_bucket_records (both NULL = all rows; rows that are not listed are neither read nor written).  Every table 16-byte aligned; an
+ * output may overlap neither an input nor another output (status 2, nothing is launched).  One launch, no allocation, no atomics. */
+#define RNAD_BEHAVIOUR_MAX 8
+int rnad_bucket_behaviour_records(const rnad_tree_t *tree, int n, const float *fast_records, const float *const *mu_rows, float *const *out,
+                                  const int32_t *rows, const int64_t *n_rows, void *stream);
+/* Distinct observations (csrc/rows_dedup.hip). What a net contributes to a (player, state) row is a function of the row's observation
  * alone (nn/net.py:37-51), so rows with the same observation share their net outputs and records, and their gradients dL/dout can be
  * added up before the backward.  The caller groups the rows by the bits of their observation (rnad_hip.TreeHandle.obs_dedup) and
  *   rnad_rows_expand      after a table launch on one representative row per group: tables[k][r] = tables[k][rep_of[r]] for every row r

@@ -130,6 +130,7 @@ class Episodes:
     _DENSE = {"mask_bits": "mask_bits", "policy": "policy", "action_idx": "actions", "rewards": "rewards"}  # attribute -> Trajectory buffer
     _observations = _values = _alive = _indices = None  # class-level defaults: objects assembled without __init__ (tests, collate) behave the same
     lane_ids = buckets = None
+    behaviour_rows = None  # a replayed batch (CompactBuffer.sample): the policy rows [2S, policy_row_stride(A)] it was played with
     _compact = None  # (rnad_hip.Trajectory(compact=True), records) of a compact bucketed rollout: dense fields expand on first access
 
     def __init__(self, tree: Tree, batch_size, seed=None, lane_offset=0, obs_half=False):
@@ -204,9 +205,13 @@ class Episodes:
     def _expand(self):
         """Dense mask_bits / policy / action_idx / rewards of a compact rollout (rnad_bucket_expand), on first access."""
         traj, records = self._compact
-        if records is None:
+        if self.behaviour_rows is not None:
+            # a replayed batch (CompactBuffer) shows the policy it was PLAYED with: the behaviour's rows, not the current records' pi
+            if traj.policy is None:
+                rnad_hip.bucket_expand(self.tree.handle(), traj, _records_of_policy_rows(self.tree.max_actions, self.behaviour_rows))
+        elif records is None:
             raise RuntimeError("this compact batch has no row records attached yet (Episodes.generate(compact=True, logits_table=...))")
-        if traj.policy is None:
+        elif traj.policy is None:
             rnad_hip.complete_records(records)  # (distinct observations: the records of the other rows of a group are copied when first read)
             rnad_hip.bucket_expand(self.tree.handle(), traj, records)
         T = self.t_eff + 1
@@ -606,3 +611,157 @@ class Buffer:
 
     def clear(self):
         self.episodes_buffer.clear()
+
+
+def _records_of_policy_rows(A, rows):
+    """A row-record table (rnad_hip.bucket_records' layout) that holds nothing but `rows` [2S, >= A] in its pi columns: what
+    rnad_bucket_expand gathers the `policy` view of a compact batch from (the masks come from the tree)."""
+    rec = torch.zeros((rows.shape[0], int(rnad_hip.lib().rnad_bucket_record_stride(A))), dtype=torch.float32, device=rows.device)
+    col = rnad_hip.policy_column(A)
+    rec[:, col: col + A] = rows[:, :A]
+    return rec
+
+
+class _Slot:
+    """One stored batch of a CompactBuffer: device buffers that are written in place by every append that lands here."""
+
+    def __init__(self, episodes, mu_shape):
+        traj, buckets = episodes._compact[0], episodes.buckets
+        self.traj = rnad_hip.Trajectory.compact_like(traj)
+        self.buckets = rnad_hip.Buckets(buckets.plan, traj.states.device)
+        self.mu = torch.empty(mu_shape, dtype=torch.float32, device=traj.states.device)
+        self.traj._owner = (episodes.tree.handle(), self.buckets)
+        view = Episodes(episodes.tree, episodes.batch_size, seed=episodes.seed, lane_offset=episodes.lane_offset, obs_half=episodes.obs_half)
+        view.finished = True
+        view._traj = self.traj
+        view.buckets, view.lane_ids = self.buckets, self.buckets.lane_ids
+        view._compact = (self.traj, None)  # (no row records: the learner takes rnad_hip.behaviour_records of `behaviour_rows`)
+        view.behaviour_rows = self.mu
+        view.states.terminal = True
+        self.view = view
+
+    def tensors(self):
+        t, b = self.traj, self.buckets
+        return [t.states, t.acts, t.final_reward, t.alive, b.items, b.n_items, b.norm, b.lane_ids, self.mu]
+
+    def store(self, episodes, mu):
+        traj, buckets = episodes._compact[0], episodes.buckets
+        alive = episodes.alive  # (completes the counts first if the rollout left them to a learner's launch)
+        self.traj.states.copy_(traj.states)
+        self.traj.acts.copy_(traj.acts)
+        self.traj.final_reward.copy_(traj.final_reward)
+        self.traj.alive.copy_(traj.alive)
+        self.buckets.items.copy_(buckets.items)
+        self.buckets.n_items.copy_(buckets.n_items)
+        self.buckets.norm.copy_(buckets.norm)
+        self.buckets.lane_ids.copy_(buckets.lane_ids)
+        self.mu[:, : mu.shape[1]].copy_(mu)
+        if mu.shape[1] < self.mu.shape[1]:
+            self.mu[:, mu.shape[1]:].zero_()
+        view = self.view
+        view.invalidate_derived()  # (the dense views of the batch this slot held before)
+        view.t_eff = episodes.t_eff
+        view.seed = view.states.seed = episodes.seed
+        view.lane_offset = view.states.lane_offset = episodes.lane_offset
+        view.alive = self.traj.alive[: episodes.t_eff + 2] if alive is not None else None
+        view.states._final_of = (self.traj, episodes.t_eff + 1)
+        view.generation_time = episodes.generation_time
+
+
+class CompactBuffer:
+    """Replay ring of COMPACT bucket-ordered batches (`Buffer`'s counterpart for RNaD.compact_replay).
+
+    A slot holds what the compact learner (rnad_hip.learn_bucketed_compact) and the dense views need of one batch as it was played:
+    the relative `states`, `acts`, `final_reward` and `alive` of its compact trajectory, the work list (`items`, `n_items`), the
+    normalisers `norm`, `lane_ids`, t_eff, seed and lane offset, and the BEHAVIOUR's policy rows [2S, policy_row_stride(A)] -- the
+    floats the rollout sampled from.  That is the trajectory's ~25 bytes per lane plus one policy table, against ~300 bytes per lane of a
+    dense batch in `Buffer`.  All `max_size` slots are allocated by the first `append` and written in place afterwards: the steady state
+    allocates nothing, and a view handed out by `sample` shows whatever its slot holds NOW.
+
+    `sample(batch_size, k)` returns k distinct stored batches, drawn uniformly with python's `random`; each is an `Episodes` view on its
+    slot (no copy) with `behaviour_rows` set, whose dense properties (`indices`, `policy`, `actions`, `rewards`, `masks`) show the batch as
+    it was played -- `policy` is the behaviour's rows gathered per slot.
+
+    The draw differs from the reference's (episode.py:315-324: B lanes across ALL stored batches -- multinomial bucket sizes, then
+    random.sample inside each batch): here a step learns from WHOLE stored batches.  Every stored lane still has the same marginal
+    probability of being learned from (k / len), but the lanes of one step share their behaviour(s).  Lane-level draws would need a
+    compaction of bucket-ordered columns and are not built.
+
+    `append` refuses, saying which: a batch that is not compact, one whose BucketPlan (or trajectory shape) is not the ring's, one whose
+    policy-row table is not valid in all 2S rows (records written for a row list -- lazy rows, row sharding --, distinct-observation tables
+    whose copies are still owed, no records attached).  Works on CPU tensors too (the bookkeeping is torch copies)."""
+
+    def __init__(self, max_size) -> None:
+        if int(max_size) < 1:
+            raise ValueError("CompactBuffer: max_size must be at least 1")
+        self.max_size = int(max_size)
+        self.plan = None
+        self._slots = []
+        self._count = 0  # stored batches
+        self._next = 0   # slot the next append writes: the oldest once the ring is full
+
+    def __len__(self):
+        return self._count
+
+    def clear(self):
+        """Forget the stored batches; the slots stay allocated."""
+        self._count = self._next = 0
+
+    @staticmethod
+    def _policy_rows_of(episodes):
+        """The policy-row table the batch was played with, valid in all 2S rows -- or a ValueError that says why there is none."""
+        compact = getattr(episodes, "_compact", None)
+        if compact is None or getattr(episodes, "buckets", None) is None:
+            raise ValueError("CompactBuffer.append: the batch is not compact (Episodes.generate(bucketed=True, compact=True) makes one)")
+        records = compact[1]
+        if records is None:
+            raise ValueError("CompactBuffer.append: the batch has no policy-row table valid in all 2S rows: no records are attached "
+                             "(a lazy-rows batch evaluates its actor on the rows it visits)")
+        if getattr(records, "_partial_rows", None) is not None:
+            raise ValueError("CompactBuffer.append: the batch has no policy-row table valid in all 2S rows: its records were written for "
+                             f"{records._partial_rows} only (lazy rows, row sharding)")
+        if getattr(records, "_expand", None) is not None:
+            raise ValueError("CompactBuffer.append: the batch has no policy-row table valid in all 2S rows: the copies of its "
+                             "distinct-observation tables have not been made (rnad_hip.rows_expand)")
+        rows = getattr(records, "_policy_rows", None)
+        if rows is not None:
+            return rows
+        if getattr(records, "_expand_job", None) is not None and getattr(records, "_expand_stale", False):
+            raise ValueError("CompactBuffer.append: the batch has no policy-row table valid in all 2S rows: the copies of its "
+                             "distinct-observation records have not been made (rnad_hip.complete_records)")
+        A = episodes.tree.max_actions
+        col = rnad_hip.policy_column(A)
+        return records[:, col: col + A]  # (records without a table of their own: their pi columns)
+
+    def append(self, episodes: Episodes):
+        """Copy a just-played compact, bucket-ordered batch into the oldest slot."""
+        mu = self._policy_rows_of(episodes)
+        traj, plan = episodes._compact[0], episodes.buckets.plan
+        if self.plan is None:
+            A = episodes.tree.max_actions
+            self.plan = plan
+            self._shape = (tuple(traj.states.shape), traj.states.dtype, int(mu.shape[0]))
+            self._slots = [_Slot(episodes, (mu.shape[0], (A + 3) & ~3)) for _ in range(self.max_size)]
+        if plan is not self.plan:
+            raise ValueError("CompactBuffer.append: the batch's BucketPlan differs from the ring's (another tree, batch size or workspace owner)")
+        if (tuple(traj.states.shape), traj.states.dtype, int(mu.shape[0])) != self._shape:
+            raise ValueError(f"CompactBuffer.append: the batch's trajectory {tuple(traj.states.shape)} {traj.states.dtype} / {int(mu.shape[0])} rows "
+                             f"differs from the ring's {self._shape}")
+        self._slots[self._next].store(episodes, mu)
+        self._next = (self._next + 1) % self.max_size
+        self._count = min(self._count + 1, self.max_size)
+
+    def sample(self, batch_size, k=1):
+        """k distinct stored batches, uniformly (python's `random`): a list of Episodes views on their slots.  batch_size must be the
+        stored batches' own: a step learns from whole batches."""
+        if self._count == 0:
+            raise ValueError("CompactBuffer.sample: the ring is empty")
+        if batch_size != self.plan.B:
+            raise ValueError(f"CompactBuffer.sample: batch_size {batch_size} is not the stored batches' {self.plan.B} (whole batches are drawn)")
+        if not 1 <= k <= self._count:
+            raise ValueError(f"CompactBuffer.sample: k = {k} distinct batches out of {self._count} stored")
+        return [self._slots[i].view for i in random.sample(range(self._count), k)]
+
+    def slot_bytes(self):
+        """Bytes one stored batch holds."""
+        return sum(t.numel() * t.element_size() for t in self._slots[0].tensors()) if self._slots else 0

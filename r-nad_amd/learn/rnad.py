@@ -158,6 +158,14 @@ class RNaD:
         # A ConvNet takes this step only when asked (True); None keeps its all-rows step.
         self.lazy_rows = None
         self.last_rows = None  # rnad_hip.LiveRows of the last lazy step
+        # Compact replay (off by default; opt-in like lazy_rows): a replay buffer of several batches (n_batches_per_buffer > 1 or
+        # buffer_mod > 1) kept as COMPACT bucket-ordered batches with the policy rows they were played with
+        # (environment.episode.CompactBuffer) and learned from, off-policy, by the compact learner on rnad_hip.behaviour_records of those
+        # rows -- instead of dense batches through Buffer.sample / Episodes.collate and the per-slot kernels.  A step learns from
+        # `replay_batches` whole stored batches (DESIGN.md section 1.8 says how that draw differs from the reference's).  Where it cannot
+        # apply (_compact_replay_refused) the trainer says so once and uses Buffer as before.
+        self.compact_replay = False
+        self.replay_batches = 1
         # clip + Adam + EMA target in one launch that also keeps the packed weight images current (csrc/optim.hip) instead of ~8 torch
         # launches and the pack launches of the next step.  None: the net family's own default (FUSED_TAIL_AUTO: on for an MLP, off for a
         # ConvNet, whose tail is opt-in); True / False force it.
@@ -1186,6 +1194,11 @@ class RNaD:
         # second trainer over the same tree and batch size -- main.py:55-81 builds several -- may step on another stream meanwhile
         with rnad_hip.workspace_owner(self._workspace_token()):
             self._leaf_watch()  # (looks at the PREVIOUS step's batch, before this step's graph key is taken)
+            if isinstance(buffer, episode.CompactBuffer):
+                why = self._compact_replay_refused()
+                if why is None:
+                    return self._replay_step(buffer, alpha, log)  # (eager: never captured)
+                buffer = self._replay_fallback(buffer, why)
             if self._graph_eligible(buffer, log):
                 return self._graph_step(buffer, alpha)
             return self._step_body(buffer, alpha, log)
@@ -1271,6 +1284,10 @@ class RNaD:
         episodes_sample = buffer.sample(local_batch)
         fused_tail = self._fused_tail()
         self.__learn(episodes_sample, alpha, log=log, tables=tables, defer_clip=fused_tail is not None)
+        self._apply_update(fused_tail, step_params)
+
+    def _apply_update(self, fused_tail, step_params=None):
+        """The tail of a step, after the gradients: clip (unless __learn did it), Adam, the EMA target (rnad.py:456, :514-523)."""
         if fused_tail is not None and self._pending_flat is not None:
             # clip + Adam + EMA target in one launch (csrc/optim.hip); a captured step also moves its queue of per-step scalars on
             fused_tail(self._pending_flat, advance=step_params)
@@ -1290,6 +1307,117 @@ class RNaD:
             src = [t for k, t in self.net.state_dict().items() if t.is_floating_point()]
             torch._foreach_mul_(tgt, 1 - self.gamma_averaging)
             torch._foreach_add_(tgt, src, alpha=self.gamma_averaging)
+
+    # ------------------------------------------------------------------ compact replay (RNaD.compact_replay)
+    def _compact_replay_refused(self):
+        """None when the compact replay step applies, else the reason it does not (a string)."""
+        if not getattr(self, "compact_replay", False):
+            return "RNaD.compact_replay is off"
+        if self._world > 1:
+            return "data-parallel replay is not built (single process only)"
+        handle = self.tree.handle()
+        T_cap, B = 2 * handle.max_depth, self.batch_size
+        if self.reuse_actor_outputs or getattr(self, "store_actor_values", False):
+            return "reuse_actor_outputs / store_actor_values need the actor's dense outputs"
+        lazy = getattr(self, "lazy_rows", None)
+        if lazy is None:
+            lazy = getattr(self.net, "LAZY_ROWS_AUTO", False) and 2 * handle.S > B
+        if lazy:
+            return "lazy rows evaluate the actor on the visited rows only: a stored batch needs its policy rows on all 2S rows"
+        if self._tabular_mode(T_cap, B) is not True:
+            return "the per-row tabular step does not apply to this net / tree / batch"
+        if not getattr(self, "compact_trajectory", True) or T_cap > rnad_hip.COMPACT_MAX_STEPS:
+            return f"the compact trajectory holds at most {rnad_hip.COMPACT_MAX_STEPS} steps"
+        if rnad_hip.bucket_plan(handle, B) is None:
+            return "this tree / batch cannot be bucketed"
+        return None
+
+    def _say_replay_refused(self, why):
+        if self.__dict__.get("_replay_refused_said") != why:
+            self._replay_refused_said = why
+            logging.warning("compact_replay not used (%s); the replay buffer is environment.episode.Buffer", why)
+
+    def _replay_fallback(self, ring, why):
+        """The Buffer that stands in for a CompactBuffer handed to a trainer whose compact replay step does not apply."""
+        self._say_replay_refused(why)
+        cached = self.__dict__.get("_replay_fallback_buffer")
+        if cached is None or cached[0] is not ring:
+            cached = self._replay_fallback_buffer = (ring, episode.Buffer(ring.max_size))
+        return cached[1]
+
+    def make_buffer(self):
+        """The replay buffer run() trains with: a CompactBuffer when compact_replay is on and applies, else the reference's Buffer."""
+        if getattr(self, "compact_replay", False):
+            why = self._compact_replay_refused()
+            if why is None:
+                return episode.CompactBuffer(self.n_batches_per_buffer)
+            self._say_replay_refused(why)
+        return episode.Buffer(self.n_batches_per_buffer)
+
+    def _replay_step(self, ring, alpha, log=None):
+        """One step with a CompactBuffer: tables and records of the current nets on all 2S rows -> (every buffer_mod steps) a compact rollout
+        with the current policy rows, appended -> `replay_batches` stored batches drawn -> ONE behaviour_records launch for their
+        behaviours -> one learn_bucketed_compact per batch with norm = None (the 64-bit sums meet in the plan's accumulators, as the
+        ranks' do under data parallelism) -> one finish with the fp64 sum of the batches' normalisers -> backward and tail as in any step.
+        A logging step learns from ONE drawn batch through __learn's dense bucketed route on its dense views (the logged statistics are
+        over per-slot tensors).  Eager."""
+        handle, A, B = self.tree.handle(), self.tree.max_actions, self.batch_size
+        k = int(getattr(self, "replay_batches", 1))
+        if k * B > rnad_hip.BUCKET_MAX_LANES:
+            raise ValueError(f"RNaD.replay_batches * batch_size = {k * B} lanes exceed the fixed-point headroom of the per-row sums "
+                             f"({rnad_hip.BUCKET_MAX_LANES} lanes per finish, csrc/bucket.hip kLaneBits)")
+        if k < 1 or k > rnad_hip.BEHAVIOUR_MAX:
+            raise ValueError(f"RNaD.replay_batches = {k} outside 1 .. {rnad_hip.BEHAVIOUR_MAX}")
+        hp = self._learn_params(alpha)
+        obs_half = getattr(self, "obs_half", False)
+        # all 2S rows: a stored batch keeps this step's policy rows, and it may visit any row of a later step's records
+        tables = self._table_outputs(alpha, obs_half, want_target_logits=log is not None, fold=self._fold(), records_hp=hp)
+        if self.total_steps % self.buffer_mod == 0 or len(ring) == 0:
+            episodes = episode.Episodes(self.tree, B, seed=self._new_seed(), lane_offset=0, obs_half=obs_half)
+            episodes.generate(self.net, trim=False, skip_absorbed=getattr(self, "skip_absorbed", True), store_values=False, tabular=True,
+                              bucketed=True, logits_table=tables["logit"], policy_table=(tables["records"], rnad_hip.policy_column(A)),
+                              compact=True)
+            if episodes._compact is None:
+                raise RuntimeError("compact_replay: the rollout of this step is not the compact bucketed one")
+            ring.append(episodes)
+            self.last_episodes = episodes
+        fused_tail = self._fused_tail()
+        if log is not None:
+            self.__learn(ring.sample(B, 1)[0], alpha, log=log, tables=tables, defer_clip=fused_tail is not None)
+            return self._apply_update(fused_tail)
+        drawn = ring.sample(B, min(k, len(ring)))
+        outs = self.__dict__.get("_replay_records")
+        if outs is None or outs[0].shape != tables["fast_records"].shape or outs[0].device != tables["fast_records"].device:
+            outs = self._replay_records = []
+        while len(outs) < len(drawn):
+            outs.append(torch.empty_like(tables["fast_records"]))
+        outs = outs[: len(drawn)]
+        rnad_hip.behaviour_records(handle, tables["fast_records"], [e.behaviour_rows for e in drawn], out=outs)
+        for e, fast in zip(drawn, outs):
+            dlogit, dv, _ = rnad_hip.learn_bucketed_compact(handle, e.buckets, e._compact[0], e.t_eff + 1, tables["records"], fast, None, hp)
+        norm = drawn[0].buckets.norm if len(drawn) == 1 else torch.stack([e.buckets.norm for e in drawn]).sum(0)
+        rnad_hip.bucket_finish(handle, drawn[0].buckets, norm, hp, dlogit, dv)
+        if getattr(self, "keep_last_tables", False):  # (tests: the per-row gradient tables of this step)
+            self.last_tables = (dlogit.clone(), dv.clone(), None)
+        weights = self.net._weights()
+        flat, views = self._grad_bucket(weights)
+        self.net.backward_rows(tables["packed_net"], tables["table"], dlogit.view(-1, A), dv.view(-1, 1), live=None, flat=flat, views=views,
+                               fold=handle if tables.get("fold", False) else False, capacity=None)
+        if all(p_.grad is None for p_ in weights):
+            for p_, g_ in zip(weights, views):
+                p_.grad = g_
+        else:  # gradient accumulation across calls, as loss.backward() would
+            for p_, g_ in zip(weights, views):
+                p_.grad = g_.clone() if p_.grad is None else p_.grad + g_
+            flat = None
+        self._pending_flat = None
+        if fused_tail is not None and flat is not None and flat.is_cuda:
+            self._pending_flat = flat  # clipped by rnad_optimizer_step together with Adam and the EMA
+        elif flat is not None and flat.is_cuda:
+            rnad_hip.clip_grad_norm(flat, self.grad_clip)  # rnad.py:456
+        else:
+            nn.utils.clip_grad_norm_(self.net.parameters(), self.grad_clip)
+        self._apply_update(fused_tail)
 
     def _fused_tail(self):
         """The net family's one-launch tail over the learner's tensors (nn/net.py optimizer_tail: clip + Adam + EMA, the packed images
@@ -1454,7 +1582,7 @@ class RNaD:
 
     # ------------------------------------------------------------------ reference learn/rnad.py:458-531
     def __resume(self, max_updates=10**6, checkpoint_mod=1000, expl_mod=1, log_mod=20) -> None:
-        buffer = episode.Buffer(self.n_batches_per_buffer)
+        buffer = self.make_buffer()  # (episode.Buffer unless compact_replay is on and applies)
         rank = self._rank
         assert self.batch_size % self._world == 0, "batch_size must be divisible by the number of GPUs"
         for _ in range(max_updates):
@@ -1462,7 +1590,8 @@ class RNaD:
             if delta_m is None:
                 return
             logging.info("m: {}, delta_m: {}".format(self.m, delta_m))
-            buffer.max_size = self.n_batches_per_buffer
+            if isinstance(buffer, episode.Buffer):
+                buffer.max_size = self.n_batches_per_buffer
 
             if self.m % expl_mod == 0 and self.n == 0 and self.m != 0:
                 if rank == 0:

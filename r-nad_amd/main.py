@@ -3,6 +3,7 @@ R-NaD for a few values of eta on the MI355X.  Lives next to the `environment / l
 reference's script lives next to its own, and uses only their reference-compatible API.
 
     python r-nad_amd/main.py [--updates 8] [--steps 100] [--batch 512] [--compact-log] [--obs-half] [--net convnet --channels 16 --depth 2 [--lazy-rows] [--fused-tail]]
+                             [--compact-replay [--replay-batches K]]
 """
 import argparse
 import logging
@@ -32,6 +33,11 @@ if __name__ == "__main__":
     ap.add_argument("--fused-tail", action="store_true",
                     help="RNaD.fused_optimizer = True: clip + Adam + EMA in one launch that keeps the packed images current (a ConvNet's opt-in; "
                          "the MLP's default)")
+    ap.add_argument("--compact-replay", action="store_true",
+                    help="RNaD.compact_replay = True: a replay buffer of compact batches with their behaviour's policy rows, learned from "
+                         "off-policy by the compact learner (environment.episode.CompactBuffer)")
+    ap.add_argument("--replay-batches", type=int, default=1, metavar="K",
+                    help="with --compact-replay: stored batches per update (RNaD.replay_batches; the buffer holds at least K)")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
     if not torch.cuda.is_available():
@@ -79,5 +85,8 @@ if __name__ == "__main__":
             trial.lazy_rows = True
         if args.fused_tail:
             trial.fused_optimizer = True
+        if args.compact_replay:
+            trial.compact_replay, trial.replay_batches = True, args.replay_batches
+            trial.n_batches_per_buffer = max(trial.n_batches_per_buffer, args.replay_batches)
         trial.run(log_mod=10, expl_mod=1, checkpoint_mod=args.steps)
         print(f"eta={eta}: NashConv by update:", [round(v, 3) for _, _, v in trial.nashconv_history])

@@ -773,6 +773,20 @@ class Trajectory:
                       self.policy.data_ptr(), self.actions.data_ptr(), self.rewards.data_ptr(), ptr(self.values),
                       self.alive.data_ptr())
 
+    @classmethod
+    def compact_like(cls, other):
+        """A compact Trajectory with buffers of `other`'s shapes, dtypes and device (a slot of environment.episode.CompactBuffer); it
+        has not been played: the caller fills the buffers and sets `_owner`."""
+        assert other.compact
+        self = cls.__new__(cls)
+        self.T_cap, self.B, self.A, self.half = other.T_cap, other.B, other.A, other.half
+        self.compact, self.device = True, other.states.device
+        self._indices = self._owner = self.c = None
+        self.observations = self.mask_bits = self.policy = self.actions = self.rewards = self.values = None
+        self.states, self.acts = torch.empty_like(other.states), torch.empty_like(other.acts)
+        self.final_reward, self.alive = torch.empty_like(other.final_reward), torch.empty_like(other.alive)
+        return self
+
     @property
     def indices(self):
         """int32 [T_cap + 1, B] (episode.py:218).  A compact trajectory rebuilds it from its relative states on first access
@@ -1652,7 +1666,45 @@ def bucket_records(tree, logit_tab, v_tab, v_target_tab, logit_reg_tab, logit_re
                                      _dp(quick, F32, "fast_records", True), _dp(pol, F32, "policy_rows", True), *_row_list(rows), _stream()))
     if pol is not None:
         rec._policy_rows = pol  # travels with the records: rollout_bucketed_compact(table=records) gathers from it
+    if rows is not None:
+        rec._partial_rows = "a row list"  # (environment.episode.CompactBuffer stores batches whose tables are valid in all 2S rows only)
     return (rec, quick) if fast else rec
+
+
+BEHAVIOUR_MAX = 8  # RNAD_BEHAVIOUR_MAX
+
+
+def behaviour_records(tree, fast_records, mu_rows_list, out=None, rows=None):
+    """rnad_bucket_behaviour_records: for every behaviour k of mu_rows_list (1 .. BEHAVIOUR_MAX tables [2S, policy_row_stride(A)]: the policy
+    rows a stored compact batch was played with) a fast-record table [2S, fast_record_stride(A)] that is `fast_records` -- this step's
+    on-policy table -- with its cs and inv_mu columns rebuilt from those rows: learn_bucketed_compact on it is the off-policy update of
+    that batch.  out: a list of tables to write into (default: fresh ones); rows: a LiveRows over the 2S rows -- only those rows are read
+    and written.  One launch for all behaviours.  Returns the list of tables."""
+    A, N = tree.A, 2 * tree.S
+    mu_rows_list = list(mu_rows_list)
+    n = len(mu_rows_list)
+    if not 1 <= n <= BEHAVIOUR_MAX:
+        raise RnadHipError(f"behaviour_records: {n} behaviours outside 1 .. {BEHAVIOUR_MAX}")
+    F, P = int(lib().rnad_bucket_fast_record_stride(A)), int(lib().rnad_bucket_policy_row_stride(A))
+    if tuple(fast_records.shape) != (N, F):
+        raise RnadHipError(f"behaviour_records: fast_records must be [{N}, {F}], got {tuple(fast_records.shape)}")
+    for k, mu in enumerate(mu_rows_list):
+        if mu is None or tuple(mu.shape) != (N, P):
+            raise RnadHipError(f"behaviour_records: mu_rows_list[{k}] must be [{N}, {P}], got {None if mu is None else tuple(mu.shape)}")
+    if out is None:
+        out = [torch.empty((N, F), dtype=F32, device=fast_records.device) for _ in range(n)]
+    out = list(out)
+    if len(out) != n:
+        raise RnadHipError(f"behaviour_records: {len(out)} output tables for {n} behaviours")
+    for k, o in enumerate(out):
+        if o is None or tuple(o.shape) != (N, F):
+            raise RnadHipError(f"behaviour_records: out[{k}] must be [{N}, {F}], got {None if o is None else tuple(o.shape)}")
+    assert rows is None or rows.N == N
+    mu_ptrs = (C.c_void_p * n)(*[_dp(mu, F32, f"mu_rows_list[{k}]").value for k, mu in enumerate(mu_rows_list)])
+    out_ptrs = (C.c_void_p * n)(*[_dp(o, F32, f"out[{k}]").value for k, o in enumerate(out)])
+    _check(lib().rnad_bucket_behaviour_records(tree.ptr, n, _dp(fast_records, F32, "fast_records"), mu_ptrs, out_ptrs, *_row_list(rows),
+                                               _stream()))
+    return out
 
 
 def complete_records(records):
@@ -1734,6 +1786,8 @@ def mlp_rows_records(tree, packed_net, packed_target, W, obs, logit_reg_tab, log
                                        _dp(quick, F32, "fast_records"), _dp(pol, F32, "policy_rows", True), _stream()))
     if pol is not None and rec is not None:
         rec._policy_rows = pol
+    if rows is not None and rec is not None:
+        rec._partial_rows = "a row list"
     return dict(logit=logit, v=v, v_target=vt, records=rec, fast_records=quick, policy_rows=pol)
 
 
