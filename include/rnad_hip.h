@@ -654,6 +654,34 @@ int rnad_bucket_records(const rnad_tree_t *tree, const float *logit_tab, const f
 #define RNAD_BEHAVIOUR_MAX 8
 int rnad_bucket_behaviour_records(const rnad_tree_t *tree, int n, const float *fast_records, const float *const *mu_rows, float *const *out,
                                   const int32_t *rows, const int64_t *n_rows, void *stream);
+/* rnad_bucket_draw_lanes (csrc/replay.hip): B lanes drawn ACROSS stored compact batches -- the draw of the reference's Buffer.sample
+ * (environment/episode.py:315-324: bucket sizes b_k, then a uniform b_k-subset of batch k) -- compacted into one bucket-ordered compact
+ * batch that rnad_learn_bucketed_compact learns from unchanged.  Source k (1 <= n <= RNAD_DRAW_MAX per call; the arrays of per-source
+ * pointers and b are HOST arrays, they travel by value in the kernel arguments) is a stored batch of the plan of (tree, B): states
+ * [T_cap + 1, B], acts, final_reward, lane_ids, items, n_items as rnad_rollout_bucketed_compact left them.  Its drawn columns are
+ * { j : sigma^-1(j) < b[k] } under the keyed bijection of include/rnad_rng.h for (seed, source0 + k, B) -- rnad_draw_columns lists them on
+ * the host, ascending, without a GPU.  They land, in their source order (a stable compaction: each stretch stays sorted by bucket), in
+ * columns [off_k, off_k + b[k]) of states_out / acts_out / final_reward_out / lane_ids_out, off_k = offset + b[0] + .. + b[k - 1]; rows of a
+ * column that the compact layout neither writes nor reads (a bucket's shared steps) are not copied.  items_out[k] / n_items_out[k]
+ * ([rnad_bucket_plan out[4]][4] / one int32 per source): the work list of that stretch, `begin` relative to the whole destination -- the drawn lanes of
+ * every bucket REPACKED into items of at most out[10] lanes, no item for a bucket without drawn lanes.  `single` is 0 unless b[k] == B
+ * (one source contributes every lane): the learner flushes a single item's table with plain stores, which would overwrite what the call for another source
+ * left in the accumulators before the one rnad_bucket_finish.  norm (f64 [2]): N_P = slots (t < T_cap, drawn column) of parity P whose
+ * state, as rnad_bucket_indices rebuilds it, is non-zero -- counted in integers; a call with offset == 0 starts the count, a call with
+ * offset > 0 (rings of more than RNAD_DRAW_MAX batches take several calls on one stream, offset = the lanes drawn so far, source0 = the
+ * sources passed so far) adds to it.  workspace: rnad_bucket_draw_workspace(tree, B) bytes, caller-owned, no content is carried between calls.
+ * Three launches, no allocation, no synchronisation, no atomics on global memory.  Refused with status 2 and nothing launched: n outside
+ * 1 .. RNAD_DRAW_MAX, a null pointer, b[k] outside 0 .. B, sum b + offset > B, a destination that overlaps a source or another
+ * destination; a tree / batch that cannot be bucketed.  The draw sizes of a whole draw should add up to B (columns beyond stay unwritten
+ * and belong to no item). */
+#define RNAD_DRAW_MAX 8
+int rnad_draw_columns(uint64_t seed, int source, int64_t B, int64_t b, int32_t *out);
+int64_t rnad_bucket_draw_workspace(const rnad_tree_t *tree, int64_t B);
+int rnad_bucket_draw_lanes(const rnad_tree_t *tree, int T_cap, int64_t B, int n, int source0, const void *const *states,
+                           const uint64_t *const *acts, const float *const *final_reward, const int32_t *const *lane_ids,
+                           const int32_t *const *items, const int32_t *const *n_items, const int64_t *b, uint64_t seed, int64_t offset,
+                           void *states_out, uint64_t *acts_out, float *final_reward_out, int32_t *lane_ids_out, int32_t *const *items_out,
+                           int32_t *const *n_items_out, double *norm, void *workspace, void *stream);
 /* Distinct observations (csrc/rows_dedup.hip). What a net contributes to a (player, state) row is a function of the row's observation
  * alone (nn/net.py:37-51), so rows with the same observation share their net outputs and records, and their gradients dL/dout can be
  * added up before the backward.  The caller groups the rows by the bits of their observation (rnad_hip.TreeHandle.obs_dedup) and

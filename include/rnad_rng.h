@@ -34,6 +34,23 @@
  *
  * rnad_exp_noise (q = -ln(u) by an fmaf-only polynomial, absolute error vs libm < 4e-8) is the
  * reproducible source of Exp(1) noise for callers of the EXPLICIT entry points.
+ *
+ * THE LANE DRAW of the compact replay (rnad_bucket_draw_lanes, csrc/replay.hip).  The reference draws
+ * b_k of the B lanes of stored batch k with random.sample (environment/episode.py:315-324): a uniform
+ * b_k-subset.  Here the subset of source k is
+ *
+ *     { sigma(i) : 0 <= i < b_k },     sigma = a keyed bijection of [0, B), a function of (seed, k, B),
+ *
+ * so column j is drawn iff sigma^-1(j) < b_k: an O(1) test per column with no sort and no per-lane
+ * state, the subset has exactly b_k members, and the subsets of b_k < b_k' are nested.  sigma is a
+ * balanced Feistel network of RNAD_DRAW_ROUNDS rounds over 2h bits, h = the smallest half width with
+ * 4^h >= B, with cycle walking (apply again while the result is >= B; the domain holds fewer than
+ * 4 B values, so fewer than four walks on average).  One round maps (L, R) to (R, L ^ F_r(R)) with
+ *
+ *     F_r(x) = philox4x32-10(counter = {x, k, r | 3 << 24, B}, key = {seed_lo, seed_hi})[0] & (2^h - 1)
+ *
+ * (the 3 << 24 keeps these counters apart from the rollout's decisions under the same seed).  Integer
+ * operations only: the host (rnad_draw_columns) and the kernels agree bit for bit.  B <= 2^30.
  */
 #ifndef RNAD_RNG_H
 #define RNAD_RNG_H
@@ -130,6 +147,64 @@ RNAD_HD int rnad_pick(const float *p, int n, float u) {
         k += c <= target ? 1 : 0;
     }
     return k;
+}
+
+/* ---- the lane draw of the compact replay (see the header comment) ---- */
+#define RNAD_DRAW_ROUNDS 6
+#define RNAD_DRAW_MAX_LANES ((int64_t)1 << 30)
+
+/* Bits of one half of the Feistel domain: the smallest h >= 1 with 4^h >= B. */
+RNAD_HD int rnad_draw_half_bits(int64_t B) {
+    int h = 1;
+    while (((int64_t)1 << (2 * h)) < B) ++h;
+    return h;
+}
+
+/* Round function r of source `source`: h bits of one philox call. */
+RNAD_HD uint32_t rnad_draw_round(uint64_t seed, uint32_t source, int64_t B, int r, uint32_t x, uint32_t half_mask) {
+    uint32_t c[4] = {x, source, (uint32_t)r | (3u << 24), (uint32_t)B};
+    rnad_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return c[0] & half_mask;
+}
+
+/* sigma(i), 0 <= i < B: the Feistel network walked until it lands inside [0, B). */
+RNAD_HD int64_t rnad_draw_sigma(uint64_t seed, uint32_t source, int64_t B, int64_t i) {
+    const int h = rnad_draw_half_bits(B);
+    const uint32_t m = (1u << h) - 1u;
+    uint32_t y = (uint32_t)i;
+    do {
+        uint32_t L = y >> h, R = y & m;
+        for (int r = 0; r < RNAD_DRAW_ROUNDS; ++r) {
+            const uint32_t n = L ^ rnad_draw_round(seed, source, B, r, R, m);
+            L = R;
+            R = n;
+        }
+        y = (L << h) | R;
+    } while ((int64_t)y >= B);
+    return (int64_t)y;
+}
+
+/* sigma^-1(j), 0 <= j < B: the rounds in reverse order, walked the same way.  Column j is drawn iff this is < b. */
+RNAD_HD int64_t rnad_draw_sigma_inv(uint64_t seed, uint32_t source, int64_t B, int64_t j) {
+    const int h = rnad_draw_half_bits(B);
+    const uint32_t m = (1u << h) - 1u;
+    uint32_t y = (uint32_t)j;
+    do {
+        uint32_t L = y >> h, R = y & m;
+        for (int r = RNAD_DRAW_ROUNDS - 1; r >= 0; --r) {
+            const uint32_t p = R ^ rnad_draw_round(seed, source, B, r, L, m);
+            R = L;
+            L = p;
+        }
+        y = (L << h) | R;
+    } while ((int64_t)y >= B);
+    return (int64_t)y;
+}
+
+RNAD_HD int rnad_draw_selected(uint64_t seed, uint32_t source, int64_t B, int64_t b, int64_t j) {
+    if (b <= 0) return 0;
+    if (b >= B) return 1;
+    return rnad_draw_sigma_inv(seed, source, B, j) < b ? 1 : 0;
 }
 
 #endif /* RNAD_RNG_H */

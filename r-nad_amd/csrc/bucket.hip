@@ -2884,6 +2884,19 @@ extern "C" int rnad_bucket_plan(const rnad_tree_t *tree, int64_t B, int64_t *out
     return 0;
 }
 
+int rnad::bucket_draw_plan(const rnad_tree_t *tree, int64_t B, const char *who, DrawPlanView &out) {
+    Plan p;
+    if (int rc = plan_for(tree, B, read_switches(), who, false, p)) return rc;
+    out.bucket_path = p.cut->bucket_path;
+    out.n_groups = p.cut->n_groups;
+    out.n_buckets = p.cut->n_buckets;
+    out.chunk = p.chunk;
+    out.rel_bytes = p.rel_bytes;
+    out.shared_root = kSharedRoot;
+    out.max_items = p.max_items;
+    return 0;
+}
+
 extern "C" int rnad_bucket_map(const rnad_tree_t *tree, int64_t B, int32_t *bucket_of, int32_t *n_groups) {
     RNAD_REQUIRE(tree && bucket_of && n_groups, "rnad_bucket_map: null argument");
     Plan p;

@@ -149,3 +149,14 @@ struct rnad_tree {
         case 8: { constexpr int kA = 8; __VA_ARGS__; } break;               \
         default: rnad::set_error("max_actions %d out of range [1,%d]", A_, RNAD_MAX_ACTIONS); return 2; \
     }
+
+namespace rnad {
+// What the lane draw of the compact replay (replay.hip) takes from the bucket plan of (tree, B); bucket.hip, which owns the planner,
+// fills it in (status 2 and an error naming `who` when this tree / batch cannot be bucketed).
+struct DrawPlanView {
+    const int32_t *bucket_path = nullptr;  // device [n_buckets] (BucketCut::bucket_path)
+    int n_groups = 0, n_buckets = 0, chunk = 0, rel_bytes = 1, shared_root = 0;  // shared_root: the flag bit of bucket_path
+    int64_t max_items = 0;
+};
+int bucket_draw_plan(const rnad_tree_t *tree, int64_t B, const char *who, DrawPlanView &out);
+}  // namespace rnad

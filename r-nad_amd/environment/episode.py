@@ -684,8 +684,9 @@ class CompactBuffer:
 
     The draw differs from the reference's (episode.py:315-324: B lanes across ALL stored batches -- multinomial bucket sizes, then
     random.sample inside each batch): here a step learns from WHOLE stored batches.  Every stored lane still has the same marginal
-    probability of being learned from (k / len), but the lanes of one step share their behaviour(s).  Lane-level draws would need a
-    compaction of bucket-ordered columns and are not built.
+    probability of being learned from (k / len), but the lanes of one step share their behaviour(s).  `sample_lanes(batch_size, seed)`
+    makes the reference's draw instead: multinomial bucket sizes over all stored batches, a uniform subset of each by a keyed bijection
+    (include/rnad_rng.h), compacted on the GPU into one draw slot (rnad_hip.draw_lanes) with one work list per contributing batch.
 
     `append` refuses, saying which: a batch that is not compact, one whose BucketPlan (or trajectory shape) is not the ring's, one whose
     policy-row table is not valid in all 2S rows (records written for a row list -- lazy rows, row sharding --, distinct-observation tables
@@ -699,6 +700,7 @@ class CompactBuffer:
         self._slots = []
         self._count = 0  # stored batches
         self._next = 0   # slot the next append writes: the oldest once the ring is full
+        self._draw = None  # the draw slot of sample_lanes (a rnad_hip.LaneDraw), allocated on first use
 
     def __len__(self):
         return self._count
@@ -761,6 +763,32 @@ class CompactBuffer:
         if not 1 <= k <= self._count:
             raise ValueError(f"CompactBuffer.sample: k = {k} distinct batches out of {self._count} stored")
         return [self._slots[i].view for i in random.sample(range(self._count), k)]
+
+    def sample_lanes(self, batch_size, seed=None):
+        """The reference's draw (Buffer.sample, episode.py:315-324): `batch_size` lanes across ALL stored batches -- bucket sizes from
+        numpy.random.multinomial(batch_size, [1 / n] * n), the very call Buffer.sample makes (the same numpy seed gives the same sizes),
+        then a uniform subset of that size inside each batch, by the keyed bijection of include/rnad_rng.h under `seed` (default: 63 bits
+        from python's `random`) instead of random.sample.  One rnad_hip.draw_lanes into a draw slot that is allocated on first use and
+        rewritten by every later call.  Returns (LaneDraw, [behaviour_rows of stored batch k]); the LaneDraw's source k is stored batch k.
+        Device tensors only."""
+        if self._count == 0:
+            raise ValueError("CompactBuffer.sample_lanes: the ring is empty")
+        if batch_size != self.plan.B:
+            raise ValueError(f"CompactBuffer.sample_lanes: batch_size {batch_size} is not the stored batches' {self.plan.B} "
+                             "(the draw slot has the stored batches' shape)")
+        slots = self._slots[: self._count]
+        if not slots[0].traj.states.is_cuda:
+            raise ValueError("CompactBuffer.sample_lanes: the ring holds CPU tensors; the lane draw runs on the GPU only (no CPU path)")
+        n = len(slots)
+        sizes = numpy.random.multinomial(batch_size, [1 / n] * n)
+        assert sum(sizes) == batch_size
+        if seed is None:
+            seed = random.getrandbits(63)
+        handle = slots[0].view.tree.handle()
+        draw = rnad_hip.draw_lanes(handle, [(s.traj, s.buckets) for s in slots], [int(b) for b in sizes], seed,
+                                   T=[s.view.t_eff + 1 for s in slots], out=self._draw)
+        self._draw = draw
+        return draw, [s.mu for s in slots]
 
     def slot_bytes(self):
         """Bytes one stored batch holds."""

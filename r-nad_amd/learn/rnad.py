@@ -166,6 +166,10 @@ class RNaD:
         # apply (_compact_replay_refused) the trainer says so once and uses Buffer as before.
         self.compact_replay = False
         self.replay_batches = 1
+        # With compact_replay: draw batch_size LANES across all stored batches per step, as the reference's Buffer.sample does (multinomial
+        # bucket sizes, a uniform subset of each batch), instead of whole batches: CompactBuffer.sample_lanes compacts them on the GPU
+        # (rnad_hip.draw_lanes) and the step learns from each contributing batch's stretch with its own behaviour.  replay_batches is ignored.
+        self.replay_lanes = False
         # clip + Adam + EMA target in one launch that also keeps the packed weight images current (csrc/optim.hip) instead of ~8 torch
         # launches and the pack launches of the next step.  None: the net family's own default (FUSED_TAIL_AUTO: on for an MLP, off for a
         # ConvNet, whose tail is opt-in); True / False force it.
@@ -1360,13 +1364,17 @@ class RNaD:
         behaviours -> one learn_bucketed_compact per batch with norm = None (the 64-bit sums meet in the plan's accumulators, as the
         ranks' do under data parallelism) -> one finish with the fp64 sum of the batches' normalisers -> backward and tail as in any step.
         A logging step learns from ONE drawn batch through __learn's dense bucketed route on its dense views (the logged statistics are
-        over per-slot tensors).  Eager."""
+        over per-slot tensors).  Eager.
+        With replay_lanes the draw is CompactBuffer.sample_lanes instead -- batch_size lanes across ALL stored batches in one compacted
+        draw slot --, one behaviour_records launch per 8 contributing behaviours, one learn_bucketed_compact per contributing batch on the
+        draw's buffers with that batch's work list, and the finish takes the draw's own normalisers."""
         handle, A, B = self.tree.handle(), self.tree.max_actions, self.batch_size
         k = int(getattr(self, "replay_batches", 1))
-        if k * B > rnad_hip.BUCKET_MAX_LANES:
+        lanes = bool(getattr(self, "replay_lanes", False))  # (B lanes per step whatever replay_batches says)
+        if not lanes and k * B > rnad_hip.BUCKET_MAX_LANES:
             raise ValueError(f"RNaD.replay_batches * batch_size = {k * B} lanes exceed the fixed-point headroom of the per-row sums "
                              f"({rnad_hip.BUCKET_MAX_LANES} lanes per finish, csrc/bucket.hip kLaneBits)")
-        if k < 1 or k > rnad_hip.BEHAVIOUR_MAX:
+        if not lanes and (k < 1 or k > rnad_hip.BEHAVIOUR_MAX):
             raise ValueError(f"RNaD.replay_batches = {k} outside 1 .. {rnad_hip.BEHAVIOUR_MAX}")
         hp = self._learn_params(alpha)
         obs_half = getattr(self, "obs_half", False)
@@ -1385,18 +1393,39 @@ class RNaD:
         if log is not None:
             self.__learn(ring.sample(B, 1)[0], alpha, log=log, tables=tables, defer_clip=fused_tail is not None)
             return self._apply_update(fused_tail)
-        drawn = ring.sample(B, min(k, len(ring)))
+        if lanes:
+            # the reference's draw: B lanes across all stored batches, compacted into the ring's draw slot; one work list per source
+            if k != 1 and not self.__dict__.get("_replay_lanes_said"):
+                self._replay_lanes_said = True
+                logging.warning("replay_lanes draws batch_size lanes across all stored batches: replay_batches = %d is ignored", k)
+            draw, rows = ring.sample_lanes(B)  # (sizes from numpy.random, the subsets' seed from python's random)
+            used = draw.contributing()
+            mus = [rows[i] for i in used]
+        else:
+            drawn = ring.sample(B, min(k, len(ring)))
+            mus = [e.behaviour_rows for e in drawn]
         outs = self.__dict__.get("_replay_records")
         if outs is None or outs[0].shape != tables["fast_records"].shape or outs[0].device != tables["fast_records"].device:
             outs = self._replay_records = []
-        while len(outs) < len(drawn):
+        while len(outs) < min(len(mus), rnad_hip.BEHAVIOUR_MAX):
             outs.append(torch.empty_like(tables["fast_records"]))
-        outs = outs[: len(drawn)]
-        rnad_hip.behaviour_records(handle, tables["fast_records"], [e.behaviour_rows for e in drawn], out=outs)
-        for e, fast in zip(drawn, outs):
-            dlogit, dv, _ = rnad_hip.learn_bucketed_compact(handle, e.buckets, e._compact[0], e.t_eff + 1, tables["records"], fast, None, hp)
-        norm = drawn[0].buckets.norm if len(drawn) == 1 else torch.stack([e.buckets.norm for e in drawn]).sum(0)
-        rnad_hip.bucket_finish(handle, drawn[0].buckets, norm, hp, dlogit, dv)
+        if lanes:
+            # one behaviour_records launch per BEHAVIOUR_MAX contributing behaviours, one learner call per contributing source on the draw's
+            # buffers with that source's work list; the sums meet in the plan's accumulators
+            for first in range(0, len(used), rnad_hip.BEHAVIOUR_MAX):
+                part = used[first: first + rnad_hip.BEHAVIOUR_MAX]
+                rnad_hip.behaviour_records(handle, tables["fast_records"], mus[first: first + len(part)], out=outs[: len(part)])
+                for i, fast in zip(part, outs):
+                    dlogit, dv, _ = rnad_hip.learn_bucketed_compact(handle, draw.buckets[i], draw.traj, draw.T[i], tables["records"], fast, None, hp)
+            norm, finish_buckets = draw.norm, draw.buckets[used[0]]
+        else:
+            outs = outs[: len(drawn)]
+            rnad_hip.behaviour_records(handle, tables["fast_records"], mus, out=outs)
+            for e, fast in zip(drawn, outs):
+                dlogit, dv, _ = rnad_hip.learn_bucketed_compact(handle, e.buckets, e._compact[0], e.t_eff + 1, tables["records"], fast, None, hp)
+            norm = drawn[0].buckets.norm if len(drawn) == 1 else torch.stack([e.buckets.norm for e in drawn]).sum(0)
+            finish_buckets = drawn[0].buckets
+        rnad_hip.bucket_finish(handle, finish_buckets, norm, hp, dlogit, dv)
         if getattr(self, "keep_last_tables", False):  # (tests: the per-row gradient tables of this step)
             self.last_tables = (dlogit.clone(), dv.clone(), None)
         weights = self.net._weights()

@@ -38,6 +38,9 @@ if __name__ == "__main__":
                          "off-policy by the compact learner (environment.episode.CompactBuffer)")
     ap.add_argument("--replay-batches", type=int, default=1, metavar="K",
                     help="with --compact-replay: stored batches per update (RNaD.replay_batches; the buffer holds at least K)")
+    ap.add_argument("--replay-lanes", action="store_true",
+                    help="with --compact-replay: RNaD.replay_lanes = True -- every update draws batch_size lanes across ALL stored batches, the "
+                         "reference's Buffer.sample, compacted on the GPU; --replay-batches is then ignored")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
     if not torch.cuda.is_available():
@@ -88,5 +91,6 @@ if __name__ == "__main__":
         if args.compact_replay:
             trial.compact_replay, trial.replay_batches = True, args.replay_batches
             trial.n_batches_per_buffer = max(trial.n_batches_per_buffer, args.replay_batches)
+            trial.replay_lanes = args.replay_lanes
         trial.run(log_mod=10, expl_mod=1, checkpoint_mod=args.steps)
         print(f"eta={eta}: NashConv by update:", [round(v, 3) for _, _, v in trial.nashconv_history])

@@ -1707,6 +1707,103 @@ def behaviour_records(tree, fast_records, mu_rows_list, out=None, rows=None):
     return out
 
 
+DRAW_MAX = 8  # RNAD_DRAW_MAX
+
+
+def draw_columns(seed, source, B, b):
+    """rnad_draw_columns: the b columns of a B-lane stored batch that the lane draw of (seed, source) selects, ascending (numpy int32;
+    host only, no GPU): { j : sigma^-1(j) < b } under the keyed bijection of include/rnad_rng.h."""
+    import numpy
+
+    out = numpy.empty((max(int(b), 0),), dtype=numpy.int32)
+    _check(lib().rnad_draw_columns(int(seed) & 0xFFFFFFFFFFFFFFFF, int(source), int(B), int(b), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+class LaneDraw:
+    """One lane draw across stored compact batches (draw_lanes): a compact Trajectory `traj` of B lanes that holds the drawn columns of
+    source 0, then of source 1, ...; `lane_ids` [B]; per source k a Buckets `buckets[k]` whose work list covers that source's stretch
+    [offsets[k], offsets[k] + sizes[k]) (`begin` is relative to the whole draw, so learn_bucketed_compact(tree, buckets[k], traj, T[k], ...)
+    learns from exactly those lanes); `norm` f64 [2], the live slots of the whole draw per parity; T[k] = t_eff + 1 of source k.  The
+    buffers are allocated once and rewritten by every draw into this holder."""
+
+    def __init__(self, tree, plan, like):
+        dev = like.states.device
+        self.tree, self.plan = tree, plan
+        self.traj = Trajectory.compact_like(like)
+        self.lane_ids = torch.empty((plan.B,), dtype=I32, device=dev)
+        self.norm = torch.zeros((2,), dtype=F64, device=dev)
+        self.workspace = torch.empty((int(lib().rnad_bucket_draw_workspace(tree.ptr, plan.B)) // 8 + 1,), dtype=torch.int64, device=dev)
+        self.buckets, self.sizes, self.offsets, self.T, self.seed = [], [], [], [], None
+
+    def _source(self, k):
+        while len(self.buckets) <= k:
+            bk = Buckets.__new__(Buckets)
+            bk.plan, bk.lane_ids, bk.norm, bk.alive_pending = self.plan, self.lane_ids, self.norm, None
+            bk.items = torch.empty((self.plan.max_items, 4), dtype=I32, device=self.lane_ids.device)
+            bk.n_items = torch.zeros((1,), dtype=I32, device=self.lane_ids.device)
+            self.buckets.append(bk)
+        return self.buckets[k]
+
+    def contributing(self):
+        """The sources that contribute lanes: [k for which sizes[k] > 0]."""
+        return [k for k, b in enumerate(self.sizes) if b > 0]
+
+
+def draw_lanes(tree, sources, sizes, seed, T=None, out=None):
+    """rnad_bucket_draw_lanes: sizes[k] lanes of stored compact batch k, for every k, compacted into one bucket-ordered compact batch.
+    sources: [(compact Trajectory, Buckets)] of ONE BucketPlan (B lanes each); sizes: ints in 0 .. B that add up to B (what
+    numpy.random.multinomial(B, [1 / n] * n) returns); seed: the draw's (the columns of source k are draw_columns(seed, k, B, sizes[k]));
+    T: each source's t_eff + 1 (kept on the result); out: a LaneDraw to draw into (default: a fresh one).  ceil(n / DRAW_MAX) calls of
+    three launches each on the current stream; no synchronisation.  Returns the LaneDraw."""
+    sources, sizes = list(sources), [int(b) for b in sizes]
+    n = len(sources)
+    if n < 1 or len(sizes) != n:
+        raise RnadHipError(f"draw_lanes: {n} sources with {len(sizes)} sizes")
+    traj0, bk0 = sources[0]
+    plan, B = bk0.plan, bk0.plan.B
+    if not traj0.states.is_cuda:
+        raise ValueError("draw_lanes: the stored batches are CPU tensors; the lane draw runs on the GPU only (no CPU path)")
+    for k, (traj, bk) in enumerate(sources):
+        if bk.plan is not plan or not traj.compact or traj.B != B or traj.states.shape != traj0.states.shape or traj.states.dtype != traj0.states.dtype:
+            raise RnadHipError(f"draw_lanes: source {k} is not a compact batch of the BucketPlan of source 0")
+        if getattr(bk, "alive_pending", None) is not None:
+            raise RnadHipError(f"draw_lanes: source {k} still owes its alive counts (bucket_alive)")
+    if any(b < 0 or b > B for b in sizes) or sum(sizes) != B:
+        raise RnadHipError(f"draw_lanes: sizes {sizes} are not counts in 0 .. {B} that add up to {B}")
+    if out is None:
+        out = LaneDraw(tree, plan, traj0)
+    if out.plan is not plan or out.traj.states.shape != traj0.states.shape or out.traj.states.dtype != traj0.states.dtype:
+        raise RnadHipError("draw_lanes: `out` was made for another BucketPlan or trajectory shape")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    dt = traj0.states.dtype
+    ptrs = lambda xs: (C.c_void_p * len(xs))(*[x.value for x in xs])  # noqa: E731
+    offset = 0
+    for first in range(0, n, DRAW_MAX):
+        part = sources[first: first + DRAW_MAX]
+        b = sizes[first: first + DRAW_MAX]
+        dst = [out._source(first + k) for k in range(len(part))]
+        _check(lib().rnad_bucket_draw_lanes(
+            tree.ptr, traj0.T_cap, B, len(part), first,
+            ptrs([_dp(t.states, dt, "states") for t, _ in part]), ptrs([_dp(t.acts, torch.int64, "acts") for t, _ in part]),
+            ptrs([_dp(t.final_reward, F32, "final_reward") for t, _ in part]), ptrs([_dp(s.lane_ids, I32, "lane_ids") for _, s in part]),
+            ptrs([_dp(s.items, I32, "items") for _, s in part]), ptrs([_dp(s.n_items, I32, "n_items") for _, s in part]),
+            (C.c_int64 * len(part))(*b), seed, offset,
+            _dp(out.traj.states, dt, "states_out"), _dp(out.traj.acts, torch.int64, "acts_out"), _dp(out.traj.final_reward, F32, "final_reward_out"),
+            _dp(out.lane_ids, I32, "lane_ids_out"), ptrs([_dp(d.items, I32, "items_out") for d in dst]),
+            ptrs([_dp(d.n_items, I32, "n_items_out") for d in dst]), _dp(out.norm, F64, "norm"), _dp(out.workspace, torch.int64, "workspace"),
+            _stream()))
+        offset += sum(b)
+    out.sizes = sizes
+    out.offsets = [sum(sizes[:k]) for k in range(n)]
+    out.T = list(T) if T is not None else [traj0.T_cap] * n
+    out.seed = seed
+    del out.buckets[n:]
+    out.traj._owner = None  # (no single work list covers the draw: indices are rebuilt per source, bucket_indices(tree, buckets[k], traj))
+    out.traj.invalidate()
+    return out
+
+
 def complete_records(records):
     """Distinct observations: the default step copies a representative's fast record and policy row to the other rows of its group (the
     rollout and the learner gather those per row) but leaves the 64-byte ROW records of the other rows to whoever reads them -- the dense

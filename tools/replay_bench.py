@@ -1,19 +1,26 @@
 #!/usr/bin/env python3
 """What a replay buffer costs per training step, and what RNaD.compact_replay makes of it: RNaD.train_step on the BASELINE configs[1]
-tree (A = 3, one outcome, depth 6: 132 862 rows) at 2^20 lanes, in five legs --
+tree (A = 3, one outcome, depth 6: 132 862 rows) at 2^20 lanes, in seven legs --
 
   (a)  the default on-policy step (a one-batch buffer refilled every step; captured as a hipGraph);
   (b)  environment.episode.Buffer with n_batches_per_buffer = 4: the off-policy path as it stands (dense batches, Buffer.sample /
        Episodes.collate, the per-slot kernels);
   (c)  compact_replay at the same settings (CompactBuffer, one stored batch per update);
   (d)  (c) with buffer_mod = 4: a rollout every fourth step;
-  (b4) (b) with buffer_mod = 4, the counterpart of (d) --
+  (b4) (b) with buffer_mod = 4, the counterpart of (d);
+  (e)  compact_replay with replay_lanes: 2^20 lanes drawn across the 4 stored batches per step (Buffer's own draw, compacted on the
+       GPU: rnad_bucket_draw_lanes), one learner launch per contributing batch;
+  (e4) (e) with buffer_mod = 4 --
 
 and the bytes one stored batch holds in (b) and in (c).  Every step is timed with a pair of device events; a leg's figure is the median
 of --steps warm steps after --warmup (min and max beside it), and the whole round of legs is repeated so that the run-to-run spread
 is visible next to the differences.  Writes a markdown report (default profiles/compact_replay.md).  Needs the MI355X.
 
     python tools/replay_bench.py [--batch-log2 20] [--depth 6] [--steps 30] [--warmup 10] [--rounds 2] [--out profiles/compact_replay.md]
+                                 [--kernels kernel_stats.csv]
+
+--kernels: the kernel_stats.csv of `rocprofv3 --kernel-trace --stats --output-format csv -- python tools/replay_bench.py --legs e ...`, a
+run of its own; the report then lists the three draw launches beside the learner and the behaviour records of that run.
 """
 import argparse
 import os
@@ -37,6 +44,8 @@ LEGS = {
     "c": dict(title="compact_replay, 4 batches", n_batches=4, buffer_mod=1, compact=True),
     "d": dict(title="compact_replay, 4 batches, buffer_mod = 4", n_batches=4, buffer_mod=4, compact=True),
     "b4": dict(title="Buffer, 4 batches, buffer_mod = 4", n_batches=4, buffer_mod=4, compact=False),
+    "e": dict(title="compact_replay + replay_lanes, 4 batches", n_batches=4, buffer_mod=1, compact=True, lanes=True),
+    "e4": dict(title="compact_replay + replay_lanes, 4 batches, buffer_mod = 4", n_batches=4, buffer_mod=4, compact=True, lanes=True),
 }
 
 
@@ -84,6 +93,7 @@ def make(leg, tree, dev, batch):
               net_params={"type": "MLP", "max_actions": tree.max_actions, "width": 256})
     rn.initialize()
     rn.compact_replay = cfg["compact"]
+    rn.replay_lanes = cfg.get("lanes", False)
     with torch.no_grad():
         for p in rn.net_reg_.parameters():
             p.mul_(1.001)
@@ -114,6 +124,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--legs", nargs="*", default=list(LEGS))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "compact_replay.md"))
+    ap.add_argument("--kernels", default=None, help="kernel_stats.csv of a rocprofv3 run of leg (e) alone")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("replay_bench: no GPU: nothing here can be measured without the MI355X")
@@ -160,6 +171,48 @@ def main():
                      f"({med['b4']:.3f} -> {med['d']:.3f} ms per step).")
     if "a" in med and "c" in med:
         lines.append(f"(c) against (a), the on-policy step: {med['c'] / med['a']:.2f} times its time ({med['a']:.3f} -> {med['c']:.3f} ms).")
+    def against(x, y, what):
+        """Ratio of leg x to leg y: of the medians over the rounds, and round by round (the between-round spread)."""
+        per_round = [statistics.median(r[x]) / statistics.median(r[y]) for r in rounds]
+        return (f"({x}) against ({y}), {what}: {med[x] / med[y]:.2f} times its time ({med[y]:.3f} -> {med[x]:.3f} ms); round by round "
+                + ", ".join(f"{q:.3f}" for q in per_round) + f" (spread {max(per_round) - min(per_round):.3f}).")
+
+    if "e" in med and "b" in med:
+        lines.append(f"(e) against (b), the only other path with the reference's draw: {med['b'] / med['e']:.2f} times "
+                     f"{'faster' if med['e'] < med['b'] else 'SLOWER'} ({med['b']:.3f} -> {med['e']:.3f} ms per step).")
+    if "e" in med and "c" in med:
+        lines.append(against("e", "c", "whole batches"))
+    if "e" in med and "a" in med:
+        lines.append(against("e", "a", "the on-policy step"))
+    if "e4" in med and "d" in med:
+        lines.append(against("e4", "d", "whole batches at buffer_mod = 4"))
+    if "e4" in med and "b4" in med:
+        lines.append(f"(e4) against (b4): {med['b4'] / med['e4']:.2f} times {'faster' if med['e4'] < med['b4'] else 'SLOWER'} "
+                     f"({med['b4']:.3f} -> {med['e4']:.3f} ms per step).")
+    if args.kernels:
+        import csv
+        import re
+
+        lines += ["", "## The launches of a lane-draw step", "",
+                  "`rocprofv3 --kernel-trace --stats` over a run of leg (e) alone (a run of its own: the step times above are not from it).", "",
+                  "| kernel | launches | average us | share of the run's kernel time |", "|---|---|---|---|"]
+        per_kernel = {}
+        for row in csv.DictReader(open(args.kernels)):
+            name = re.sub(r"\(anonymous namespace\)::", "", row["Name"])
+            if re.search(r"k_draw_|k_bucket_learn_c|k_behaviour_records|k_bucket_finish", name):
+                short = re.sub(r"\(.*", "", re.sub(r"^void ", "", name))
+                lines.append(f"| `{short}` | {row['Calls']} | {float(row['AverageNs']) / 1e3:.1f} | {float(row['Percentage']):.1f} % |")
+                per_kernel[short.split("<")[0].split("::")[-1]] = (int(row["Calls"]), float(row["TotalDurationNs"]) / 1e3)
+        if "k_draw_scan" in per_kernel and "k_bucket_learn_c" in per_kernel:
+            steps = per_kernel["k_draw_scan"][0]  # (one scan launch per draw call, one draw call per step with <= 8 stored batches)
+            draw = {k: v[1] / steps for k, v in per_kernel.items() if k.startswith("k_draw_")}
+            learn = per_kernel["k_bucket_learn_c"][1] / steps
+            worst = max(draw, key=draw.get)
+            lines += ["", f"Per step: the three draw launches {sum(draw.values()):.1f} us ("
+                      + ", ".join(f"`{k}` {v:.1f}" for k, v in sorted(draw.items())) + f"), the learner launches {learn:.1f} us "
+                      f"({per_kernel['k_bucket_learn_c'][0] / steps:.2f} per step).  "
+                      + (f"The draw costs more than the learner it feeds; `{worst}` is the largest part of it."
+                         if sum(draw.values()) > learn else "The draw costs less than the learner it feeds.")]
     lines.append("")
     lines.append("## Bytes held per stored batch")
     lines.append("")
