@@ -984,6 +984,50 @@ int rnad_reg_evaluate(const rnad_tree_t *tree, int n, const float *eta, const fl
                       float *q, float *residual, float *reach, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact counterfactual regret minimisation  --  no counterpart in the reference.  Every state of
+ * these trees is its own information set for both players, so tabular CFR is exact.  One call is
+ * one iteration for each of n members (variants run in lockstep on one read of the transition
+ * tables).  Tables f32 [S][n][2A] in the orientation of rnad_reg_evaluate: entries [:A] are the row
+ * player's, entries [A:] the column player's.  For member k with discount[k] = (dp, dn, da), in
+ * this order of operations:
+ *   sigma[s,side,a] = R+(a) / sum R+ over the side's legal actions (a ascending) where the sum is
+ *                     > 0, else 1 / (the number of the side's legal actions); R+ = max(R, 0);
+ *                     0 on illegal actions               (from the regrets as they stand: sigma_t)
+ * top-down, reach[1] = (1, 1, 1), for every live link (chance > 0 and next != 0) from s to u:
+ *   reach_row[u] = reach_row[s] * sigma[s, r]           reach_col[u] = reach_col[s] * sigma[s, A + c]
+ *   reach_chance[u] = reach_chance[s] * chance
+ * bottom-up over level_order, V[0] = 0:
+ *   Q[s,r,c]   = sum_t chance[s,t,r,c] * (next == 0 ? value[s,t,r,c] : values[next, k])
+ *   q0[r]      = sum_c Q[s,r,c] * sigma[s, A + c]       q1[c] = -(sum_r Q[s,r,c] * sigma[s, r])
+ *   values[s,k] = v = sum_r sigma[s,r] * q0[r]          the column side's q is in its OWN payoff
+ *   for a side whose bit is set in sides[k] (bit 0: row, bit 1: column), on its legal actions,
+ *   with cf_row = reach_col * reach_chance, cf_col = reach_row * reach_chance, v_row = v, v_col = -v:
+ *     regret[a]       <- (regret[a] > 0 ? dp : dn) * regret[a] + cf_side * (q_side[a] - v_side)
+ *     strategy_sum[a] <- da * strategy_sum[a] + own_reach_side * sigma_side[a]
+ * (dp, dn, da) = (1, 1, 1) is plain CFR; dn = 0 gives the regrets of CFR+ (zeroing the negatives
+ * before the add leaves the same R+ as clamping after it); da = (t - 1) / t averages with weights
+ * proportional to t; DCFR(alpha, beta, gamma) takes t^alpha / (t^alpha + 1), t^beta / (t^beta + 1)
+ * and (t / (t + 1))^gamma of the previous t.  The index tensor must be a tree, as for
+ * rnad_best_response.
+ * discount f32 [n][3] and sides i32 [n] are DEVICE arrays read by the kernels -- they change every
+ * iteration, and a captured call follows them when the caller rewrites them between replays.
+ * regret, strategy_sum: in/out; a side whose bit is clear keeps its rows bit for bit, and entries
+ * of illegal actions, state 0 and states no live path reaches are never written.  Outputs, all
+ * three required and the caller's: policy f32 [S][n][2A] (sigma_t), values f32 [S][n], reach
+ * f32 [S][3][n] (row-own, column-own, chance); every row is written -- state 0 and states no live
+ * path reaches with zeros -- and nothing is allocated or cleared otherwise.  One launch that writes
+ * those rows and the root's reach, one per level top-down, one per level bottom-up, on `stream`;
+ * no atomics and a fixed order of operations: the same inputs give the same bits and the call can
+ * be captured in a hipGraph.  Refused on the host: a null pointer, n outside
+ * [1, RNAD_CROSS_PLAY_MAX], a table or an output that overlaps any other buffer.
+ * rnad_cfr_size (host only): floats of `reach` = 3 * S * n; -1 unless S >= 2 and
+ * 1 <= n <= RNAD_CROSS_PLAY_MAX.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t rnad_cfr_size(int64_t S, int n);
+int rnad_cfr_iterate(const rnad_tree_t *tree, int n, const float *discount, const int32_t *sides, float *regret, float *strategy_sum,
+                     float *policy, float *values, float *reach, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact expected learner update  --  no counterpart in the reference, whose learner computes its
  * value targets and action values from sampled games (two-player V-trace, learn/vtrace.py:206-322).
  * For each of n members -- behaviour table mu, evaluated policy pip (pi_processed), lpol =

@@ -480,6 +480,17 @@ class RNaD:
             raise ValueError("tabular_baseline: eta = 0: the unregularised game has no unique fixed point to sweep to")
         return list(tabular.TabularRNaD(self.tree, self.eta).run(updates))
 
+    def cfr_baseline(self, iterations: int, variant="cfr+", every: int = 1):
+        """(recorded iterations, NashConv of the average policy at each) of `iterations` exact CFR iterations of `variant` on this
+        trainer's tree (learn.tabular.TabularCFR): what counterfactual regret minimisation reaches on the tree the net is trained on.
+        Unlike tabular_baseline, which returns the plain list of one figure per update, this returns a pair: with every > 1 not every
+        iteration is recorded, so the curve comes with the iterations it was taken at."""
+        from learn import tabular
+
+        cfr = tabular.TabularCFR(self.tree, variant)
+        cfr.run(iterations, every=every)
+        return list(cfr.recorded), list(cfr.average_nashconv_history[0])
+
     def inner_progress(self, alpha=None):
         """How far the inner loop is from the fixed point its current magnet defines: learn.tabular.evaluate_regularized of
         [net, net_target] at this trainer's eta against alpha * log pi_reg + (1 - alpha) * log pi_reg_ (:382), exactly, on the whole tree.

@@ -10,6 +10,10 @@ sampling noise, off-policy correction and function approximation taken out.  The
 `evaluate_regularized` answers the question in between: how far is an ARBITRARY policy from the fixed point its magnet defines, and what
 is it worth there (rnad_reg_evaluate, csrc/reg_evaluate.hip) -- the quantities the learner estimates by sampling.  `TabularNeuRD` is the
 exact inner loop built on it: NeuRD steps on a logit table, between `TabularRNaD` (no inner loop) and the sampled trainer.
+
+`TabularCFR` runs the algorithm the field puts beside R-NaD on the same tree: counterfactual regret minimisation, exact because every
+state is its own information set for both players (rnad_cfr_iterate, csrc/cfr.hip) -- plain CFR, CFR+, linear averaging and DCFR, up to
+32 variants in lockstep, judged by the same NashConv.
 """
 from typing import List, NamedTuple
 
@@ -309,3 +313,167 @@ class TabularNeuRD:
         self.log_reg = torch.where(self.logits > float("-inf"), _log_softmax_support(self.logits), self.logits).contiguous()
         self.logits = self.log_reg.clone()
         self.evaluation = None
+
+
+# ---------------------------------------------------------------------------------------------------- exact CFR
+CFR_VARIANTS = ("cfr", "cfr+", "linear")
+
+
+def _ratio(x: int, e: float) -> float:
+    """x^e / (x^e + 1) for an integer x >= 0, with the limits at x = 0 and e = -inf."""
+    if x == 0:
+        return 0.0 if e > 0 else (0.5 if e == 0 else 1.0)
+    p = float(x) ** e
+    return p / (p + 1.0)
+
+
+def cfr_discounts(variant, t: int):
+    """(dp, dn, da) of iteration t >= 1 in fp64 (rnad_cfr_iterate): what the accumulated regrets (positive, negative) and the strategy sum
+    are multiplied by before iteration t's terms are added.  "cfr": (1, 1, 1).  "cfr+": (1, 0, (t - 1) / t) -- the negatives are zeroed
+    before the add, which leaves the same R+ as clamping after it, and the average weighs iteration t by t as its authors do.
+    "linear": (1, 1, (t - 1) / t).  ("dcfr", alpha, beta, gamma): (x^alpha / (x^alpha + 1), x^beta / (x^beta + 1), (x / (x + 1))^gamma) at
+    x = t - 1."""
+    t = int(t)
+    if variant == "cfr":
+        return 1.0, 1.0, 1.0
+    if variant == "cfr+":
+        return 1.0, 0.0, (t - 1) / t
+    if variant == "linear":
+        return 1.0, 1.0, (t - 1) / t
+    _, alpha, beta, gamma = variant
+    return _ratio(t - 1, alpha), _ratio(t - 1, beta), ((t - 1) / t) ** gamma
+
+
+def _cfr_variant(v):
+    if isinstance(v, str) and v in CFR_VARIANTS:
+        return v
+    if isinstance(v, (tuple, list)) and len(v) == 4 and v[0] == "dcfr":
+        try:
+            alpha, beta, gamma = (float(x) for x in v[1:])
+        except (TypeError, ValueError):
+            alpha = beta = gamma = float("nan")
+        if alpha == alpha and beta == beta and gamma == gamma:
+            return ("dcfr", alpha, beta, gamma)
+    raise ValueError(f"TabularCFR: unknown variant {v!r}: expected one of {CFR_VARIANTS} or ('dcfr', alpha, beta, gamma)")
+
+
+def normalised_per_side(tree, table) -> torch.Tensor:
+    """[S, n, 2A]: a nonnegative table normalised per side over the legal actions, uniform over them where the side's sum is 0, zero on
+    illegal actions."""
+    A = tree.max_actions
+    mask = legal_mask(tree)[:, None, :]
+    x = torch.where(mask, table, torch.zeros_like(table))
+    halves = []
+    for lo in (0, A):
+        h, on = x[..., lo:lo + A], mask[..., lo:lo + A]
+        tot = h.sum(-1, keepdim=True)
+        cnt = on.sum(-1, keepdim=True).clamp(min=1).to(h.dtype)
+        halves.append(torch.where(on, torch.where(tot > 0, h / torch.where(tot > 0, tot, torch.ones_like(tot)), 1.0 / cnt), torch.zeros_like(h)))
+    return torch.cat(halves, dim=-1)
+
+
+class TabularCFR:
+    """Counterfactual regret minimisation on the enumerated tree, exactly: every state is its own information set for both players, so
+    one iteration is one top-down and one bottom-up sweep (rnad_cfr_iterate, csrc/cfr.hip), and up to 32 variants run in lockstep on one
+    read of the transition tables.  variants: one name or a list; each "cfr", "cfr+", "linear" or ("dcfr", alpha, beta, gamma)
+    (cfr_discounts).  alternating: one bool or one per member, default True for "cfr+" and False otherwise; an alternating member updates
+    the row side on odd iterations and the column side on even ones.  The discounts are computed in fp64 on the host per iteration,
+    rounded to fp32 and written to the device tensors the kernels read.  step() runs one iteration; run(iterations, every) records
+    nashconv_history[k] (the current policy sigma_t) and average_nashconv_history[k] at the iterations in `recorded`.  regret,
+    strategy_sum [S, n, 2A]; policy (sigma of the last iteration), values [S, n], reach [S, 3, n] after the first step; average_policy
+    [S, n, 2A]: strategy_sum normalised per side, uniform over the legal actions where the sum is 0 -- average_policy[:, k] is an ordinary
+    policy table for util.metric.cross_play, best_response, mixture, evaluate_regularized and TabularRNaD(reg=...)."""
+
+    def __init__(self, tree, variants="cfr+", alternating=None):
+        if not metric.index_is_tree(tree):
+            raise ValueError("TabularCFR: the index tensor is not a tree: own-action reach is undefined (a state with two parents has no "
+                             "perfect recall, and its reach values would race)")
+        many = isinstance(variants, list) or (isinstance(variants, tuple) and not (len(variants) == 4 and variants[0] == "dcfr"))
+        self.variants = [_cfr_variant(v) for v in (variants if many else [variants])]
+        n = len(self.variants)
+        if not 1 <= n <= rnad_hip.CROSS_PLAY_MAX:
+            raise ValueError(f"TabularCFR: {n} variants outside [1, {rnad_hip.CROSS_PLAY_MAX}]")
+        if alternating is None:
+            self.alternating = [v == "cfr+" for v in self.variants]
+        elif isinstance(alternating, (list, tuple)):
+            if len(alternating) != n:
+                raise ValueError(f"TabularCFR: {len(alternating)} values of alternating for {n} variants")
+            self.alternating = [bool(a) for a in alternating]
+        else:
+            self.alternating = [bool(alternating)] * n
+        self.tree, self.n, self.t = tree, n, 0
+        S, A, dev = tree.value_tensor.shape[0], tree.max_actions, tree.value_tensor.device
+        self.regret = torch.zeros((S, n, 2 * A), dtype=torch.float, device=dev)
+        self.strategy_sum = torch.zeros((S, n, 2 * A), dtype=torch.float, device=dev)
+        # the per-iteration parameters share one device buffer of 4n words, so that an iteration costs one host-to-device copy
+        self._step_words = torch.empty((4 * n,), dtype=torch.int32, device=dev)
+        self.discount = self._step_words[:3 * n].view(torch.float).view(n, 3)
+        self.sides = self._step_words[3 * n:]
+        self.discount.fill_(1.0)
+        self.sides.fill_(3)
+        self._policy = torch.empty((S, n, 2 * A), dtype=torch.float, device=dev)
+        self._values = torch.empty((S, n), dtype=torch.float, device=dev)
+        self._reach = torch.empty((S, 3, n), dtype=torch.float, device=dev)
+        self._data = metric.NashConvData(tree)
+        self.recorded: List[int] = []
+        self.nashconv_history: List[List[float]] = [[] for _ in range(n)]
+        self.average_nashconv_history: List[List[float]] = [[] for _ in range(n)]
+
+    def _ran(self, what):
+        if self.t == 0:
+            raise ValueError(f"TabularCFR.{what}: no iteration has run yet")
+
+    @property
+    def policy(self) -> torch.Tensor:
+        """[S, n, 2A]: sigma of the last iteration."""
+        self._ran("policy")
+        return self._policy
+
+    @property
+    def values(self) -> torch.Tensor:
+        self._ran("values")
+        return self._values
+
+    @property
+    def reach(self) -> torch.Tensor:
+        self._ran("reach")
+        return self._reach
+
+    @property
+    def average_policy(self) -> torch.Tensor:
+        return normalised_per_side(self.tree, self.strategy_sum)
+
+    def set_iteration(self, t: int) -> None:
+        """Write iteration t's discounts and side bits to the device tensors."""
+        disc = torch.tensor([cfr_discounts(v, t) for v in self.variants], dtype=torch.float64).to(torch.float)
+        turn = torch.tensor([(1 if t % 2 == 1 else 2) if a else 3 for a in self.alternating], dtype=torch.int32)
+        self._step_words.copy_(torch.cat([disc.reshape(-1).view(torch.int32), turn]))
+
+    def step(self) -> None:
+        self.set_iteration(self.t + 1)
+        rnad_hip.cfr_iterate(self.tree.handle(), self.regret, self.strategy_sum, self.discount, self.sides, self._policy, self._values,
+                             self._reach)
+        self.t += 1
+
+    def _nashconv(self, table) -> float:
+        self._data.joint_policy.copy_(table)
+        self._data.get_nashconv(self.tree, self._data.joint_policy)
+        return (self._data.row_best[1] + self._data.col_best[1]).item()
+
+    def record(self) -> None:
+        """NashConv of every member's current and average policy at this iteration."""
+        self._ran("record")
+        average = self.average_policy
+        self.recorded.append(self.t)
+        for k in range(self.n):
+            self.nashconv_history[k].append(self._nashconv(self._policy[:, k]))
+            self.average_nashconv_history[k].append(self._nashconv(average[:, k]))
+
+    def run(self, iterations: int, every: int = 1) -> List[List[float]]:
+        """`iterations` more iterations, recording after every `every`-th of them and after the last; returns average_nashconv_history."""
+        every = max(1, int(every))
+        for i in range(1, int(iterations) + 1):
+            self.step()
+            if i % every == 0 or i == int(iterations):
+                self.record()
+        return self.average_nashconv_history

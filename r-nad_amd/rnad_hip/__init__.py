@@ -2234,6 +2234,46 @@ def reg_evaluate(tree, eta, policies, log_reg, values=None, q=None, residual=Non
     return tuple(outs)
 
 
+def cfr_iterate(tree, regret, strategy_sum, discount, sides, policy=None, values=None, reach=None):
+    """rnad_cfr_iterate: one exact CFR iteration for each of n members on the enumerated tree.  regret, strategy_sum f32 [S, n, 2A], updated
+    in place (rows [:A] the row player's, [A:] the column player's); discount f32 [n, 3] = (dp, dn, da) per member and sides i32 [n]
+    (bit 0: the row side updates, bit 1: the column side) on the DEVICE -> (policy f32 [S, n, 2A]: sigma_t, regret matching on the regrets
+    as they came in; values f32 [S, n]: the row player's value of sigma_t; reach f32 [S, 3, n]: row-own, column-own and chance reach of
+    sigma_t).  The three outputs may be given as existing buffers (every row is written).  With all three given nothing is allocated:
+    capturable, and a captured call reads discount and sides anew at every replay."""
+    if not torch.is_tensor(regret) or regret.dim() != 3:
+        raise RnadHipError("cfr_iterate: regret must be a tensor of shape [S, n, 2A]")
+    rp = _dp(regret, F32, "regret")
+    if not isinstance(tree, TreeHandle):
+        raise RnadHipError("cfr_iterate: tree must be a TreeHandle (Tree.handle())")
+    S, n, A2 = regret.shape
+    if S != tree.S or A2 != 2 * tree.A:
+        raise RnadHipError(f"cfr_iterate: regret of shape {tuple(regret.shape)} does not fit a tree of {tree.S} states and {tree.A} "
+                           f"actions (expected [{tree.S}, n, {2 * tree.A}])")
+    if lib().rnad_cfr_size(S, n) < 0:
+        raise RnadHipError(f"cfr_iterate: {n} members outside [1, {CROSS_PLAY_MAX}]")
+    if regret.get_device() != (tree.device.index if tree.device.index is not None else torch.cuda.current_device()):
+        raise RnadHipError(f"cfr_iterate: regret lives on {regret.device}, the tree's tables on {tree.device}")
+    bufs, ptrs = [("regret", regret)], []
+    for name, given, shape, dtype in (("strategy_sum", strategy_sum, (S, n, A2), F32), ("discount", discount, (n, 3), F32),
+                                      ("sides", sides, (n,), I32), ("policy", policy, (S, n, A2), F32), ("values", values, (S, n), F32),
+                                      ("reach", reach, (S, 3, n), F32)):
+        t = torch.empty(shape, dtype=dtype, device=regret.device) if given is None and name in ("policy", "values", "reach") else given
+        if not torch.is_tensor(t):
+            raise RnadHipError(f"cfr_iterate: {name} must be a tensor of shape {list(shape)}")
+        ptrs.append(_dp(t, dtype, name))
+        if tuple(t.shape) != shape or t.device != regret.device:
+            raise RnadHipError(f"cfr_iterate: {name} must be {list(shape)} on {regret.device}, got {list(t.shape)} on {t.device}")
+        for other_name, other in bufs:
+            lo, hi = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
+            if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+                raise RnadHipError(f"cfr_iterate: {name} aliases {other_name} (the buffers overlap)")
+        bufs.append((name, t))
+    sp, dp_, ip, pp, vp, hp = ptrs
+    _check(lib().rnad_cfr_iterate(tree.ptr, n, dp_, ip, rp, sp, pp, vp, hp, _stream()))
+    return bufs[4][1], bufs[5][1], bufs[6][1]
+
+
 def _vtrace_inputs(what, tree, hyper, mu, pip, lpol, vv):
     """The argument checks rnad_vtrace_expect and rnad_vtrace_moments share -> (S, n, A, [(name, tensor)], [pointers], hyper as C floats)."""
     if not torch.is_tensor(mu) or mu.dim() != 3:
@@ -2393,6 +2433,48 @@ def source_hash():
         with open(f, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+def kernel_notes(marker, so_path=None):
+    """The amdhsa.kernels metadata records ({'.name': ..., '.vgpr_count': ..., ...}, values as strings) of every gfx950 code object of
+    the built library whose bundle holds the bytes `marker` (a kernel's name): .hip_fatbin -> its offload bundles -> the code object ->
+    its notes, through ROCm's llvm-objcopy, clang-offload-bundler and llvm-readobj.  None where those tools are not installed."""
+    import re
+    import subprocess
+    import tempfile
+
+    llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
+    tools = {t: os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readobj")}
+    if not all(os.path.exists(p) for p in tools.values()):
+        return None
+    marker = marker.encode() if isinstance(marker, str) else marker
+    kernels = []
+    with tempfile.TemporaryDirectory(prefix="rnad_notes_") as tmp:
+        fat = os.path.join(tmp, "fat.bin")
+        subprocess.check_call([tools["llvm-objcopy"], f"--dump-section=.hip_fatbin={fat}", os.path.realpath(so_path or SO_PATH),
+                               os.path.join(tmp, "copy.so")])
+        blob = open(fat, "rb").read()
+        starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), blob)]
+        for i, s in enumerate(starts):
+            part = blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)]
+            if marker not in part:
+                continue
+            bundle, co = os.path.join(tmp, f"b{i}.bin"), os.path.join(tmp, f"b{i}.co")
+            with open(bundle, "wb") as f:
+                f.write(part)
+            subprocess.check_call([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                                   f"--input={bundle}", f"--output={co}"])
+            cur = None
+            for line in subprocess.check_output([tools["llvm-readobj"], "--notes", co], text=True).splitlines():
+                m = re.match(r"^\s{2}(?:- |\s{2})(\.\w+):\s*(.*)$", line)
+                if not m:
+                    continue
+                if line.lstrip().startswith("- "):
+                    cur = {}
+                    kernels.append(cur)
+                if cur is not None:
+                    cur[m.group(1)] = m.group(2).strip().strip("'\"")
+    return kernels
 
 
 def prof_enable(on):
